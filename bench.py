@@ -11,6 +11,10 @@ torch.distributed.run launched them (WORLD_SIZE is set), or this process starts 
 contiguous chunk of the sequence, started with ``initialImage``: weak scaling, no
 data-path collective.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line with the timed region's own figures.  ``--full`` adds the
+passes and legs after the timed region (per-kernel passes, sequence_start, sustained, exact_f32, f16_fast_mode, cpu_baseline and
+parity).  ``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (``dump_outputs``).
+
 Two further modes time the collectives SURVEY.md 8(e) defines (each prints its own JSON line, with its own metric):
 
     --mode train   BASELINE config #3: the mainVideoUnshaded.py step (B=16 clips x T=10 frames, 32^2 -> 128^2 crops, l1 +
@@ -109,7 +113,42 @@ def parse(argv=None):
     ap.add_argument("--graph", action="store_true", help="steady-state frames replay as one HIP graph each (pipeline.py); the per-kernel "
                     "durations of `roofline` / `kernels` then come from an eager pass of the same frames AFTER the timed region "
                     "(a replayed graph has no per-dispatch events)")
+    ap.add_argument("--full", action="store_true", help="default mode: after the timed region also run the legs the headline does not need -- "
+                    "the per-kernel passes (`kernels` complete, `frame_time`, the ray-march alone), sequence_start, sustained, the exact-fp32 "
+                    "and fp16 legs, the CPU baseline with its parity passes.  Without it the line is the timed region's own figures")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32, or float64 where the value is float64), at most %d MB in all: larger outputs are cut to a fixed seeded "
+                    "sample of their elements" % (DUMP_BUDGET_BYTES // 10**6))
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, arrays):
+    """Write ``{name: tensor or array}`` as ``directory/<name>.npy`` (float64 stays float64, everything else becomes float32).  The
+    arrays are taken smallest first; one that does not fit its even share of what is left of DUMP_BUDGET_BYTES is written as a sample
+    of its flattened elements: sorted indices drawn without replacement by numpy's generator seeded with DUMP_SEED, so that two runs
+    of the same command -- and two builds -- write the same elements.  Returns {name: description} (printed to stderr)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    left, written = DUMP_BUDGET_BYTES, {}
+    for i, (name, a) in enumerate(sorted(host.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(host) - i)
+        if a.nbytes <= share:
+            out, written[name] = a, "whole, shape %s" % (list(a.shape),)
+        else:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False))
+            out, written[name] = a.reshape(-1)[idx], "%d of the %d elements of shape %s (flattened, seed %d)" % (k, a.size, list(a.shape), DUMP_SEED)
+        np.save(os.path.join(directory, name + ".npy"), out)
+        left -= out.nbytes
+    return written
 
 
 class Job:
@@ -403,14 +442,17 @@ def run_infer(args, job):
     th = t0
     for k in range(K):
         # the next frame's ray-march is enqueued on a side stream and overlaps this frame's network
-        pipe.frame(origins[Wm + k], origins[Wm + k + 1] if overlap else None)
+        rgb, raw = pipe.frame(origins[Wm + k], origins[Wm + k + 1] if overlap else None)
         tn = time.perf_counter()
         host_ms.append((tn - th) * 1e3)
         th = tn
     sync()
     elapsed = time.perf_counter() - t0
     graph_replays = pipe.graph_replays - replays0
-    if pipe.graph:
+    if args.dump_outputs and rank == 0 and K > 0:
+        # the last timed frame, before any later pass reuses the pipeline's output buffers
+        sys.stderr.write("bench.py: --dump-outputs %s\n" % json.dumps(dump_outputs(args.dump_outputs, {"rgb": rgb, "raw": raw})))
+    if pipe.graph and args.full:
         # the per-kernel pass: the same K frames launched eagerly with the dispatch-packet events on (outside the timed region)
         pipe.graph = False
         pipe.reset()
@@ -421,7 +463,7 @@ def run_infer(args, job):
         sync()
         pipe.graph = True
     records = ops.profile_records()
-    if prof_timed and not prof_small_timed:
+    if prof_timed and not prof_small_timed and args.full:
         # the small kernels' durations: the same frames once more, eagerly, outside the timed region
         n_small = min(K, 10)
         pipe.reset()
@@ -453,8 +495,8 @@ def run_infer(args, job):
     rm_time = sum(rm_ms) * 1e-3 / max(1, len(rm_ms))
     # the ray-marcher on its own (outside the timed region): the kernel's own figure, next to the one it has as a
     # one-wave-per-SIMD guest under the network
-    rm_alone = rm_time
-    if overlap:
+    rm_alone = None if overlap else rm_time
+    if overlap and args.full:
         gb = torch.empty((low_h, low_w, 12), dtype=torch.float32, device="cuda")
         renderer.set_kernel_variant(args.raymarch_variant)
         renderer.profile_enable(True)
@@ -532,21 +574,25 @@ def run_infer(args, job):
                         "frac": (v[0] / v[1] / 1e12 / ((MFMA_F16_PEAK_TFLOPS / 3.0) if is_split_kernel(n)
                                                        else MFMA_F32_PEAK_TFLOPS)) if v[0] > 0 else None}      # None: no matrix work (assembly, packing, finishing)
                     for n, v in per.items()},
-        # the frame's time that is NOT inside a main-stream kernel, and the host's share (an outlier run explains itself from this)
-        "frame_time": gap_accounting(elapsed / K * 1e3, per, K, host_ms) if prof_timed or pipe.graph else None,
+        # the frame's time that is NOT inside a main-stream kernel, and the host's share (an outlier run explains itself from this);
+        # it needs every kernel's duration: the small kernels' pass runs with --full only (BENCH_PROFILE_SMALL=1 times them in the region)
+        "frame_time": gap_accounting(elapsed / K * 1e3, per, K, host_ms)
+                      if (prof_timed or pipe.graph) and (args.full or prof_small_timed) else None,
         "raymarch": {"kernel": "iso_render_gather (on a side stream under the network)" if overlap else "iso_render_gather",
-                     "ms_per_frame": rm_time * 1e3, "alone_ms_per_frame": rm_alone * 1e3},
+                     "ms_per_frame": rm_time * 1e3, "alone_ms_per_frame": rm_alone * 1e3 if rm_alone is not None else None},
+        # what the line leaves out without --full (the legs below, and the per-kernel passes behind `kernels` / `frame_time`)
+        "full": bool(args.full),
     }
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         result["sequence_start"] = sequence_start_leg(pipe, origins, Wm, overlap, sync)
-    if rank == 0 and world == 1 and args.sustained_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.sustained_frames > 0:
         result["sustained"] = sustained_leg(pipe, args.sustained_frames, max(64, world * K), overlap, sync)
-    if rank == 0 and world == 1 and not args.exact and not args.no_exact_leg:
+    if args.full and rank == 0 and world == 1 and not args.exact and not args.no_exact_leg:
         result["exact_f32"] = exact_leg(pipe, origins, Wm, K, overlap, sync)
-    if rank == 0 and world == 1 and not args.no_fast_mode:
+    if args.full and rank == 0 and world == 1 and not args.no_fast_mode:
         result["f16_fast_mode"] = fast_mode_leg(pipe, origins, Wm, K, overlap, sync)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result.update(cpu_reference_leg(args, vol, iso, net, pipe, origins[Wm], low_w, low_h, result, rm_alone))
     if rank == 0 and world == 1 and args.raymarch_large:
         result["raymarch_large"] = raymarch_large_leg(args.raymarch_large, renderer)
@@ -605,6 +651,10 @@ def run_train(args, job):
     job.sync()
     elapsed = job.max_over_ranks(time.perf_counter() - t0)
     loss = float(loss)
+    if args.dump_outputs and rank == 0 and K > 0:
+        # the last timed step's loss and the weights it left (before the eager per-kernel step below moves them again)
+        sys.stderr.write("bench.py: --dump-outputs %s\n" % json.dumps(dump_outputs(args.dump_outputs, {
+            "loss": torch.tensor([loss], dtype=torch.float64), "parameters": torch.cat([p.detach().reshape(-1) for p in net.parameters()])})))
     # the collective on its own: the flat gradient bucket, as in the step
     allreduce = None
     if world > 1:
@@ -826,6 +876,8 @@ def run_tiled(args, job, make_local_renderer=None):
     elapsed = job.max_over_ranks(time.perf_counter() - t0)
     if dev == "cuda":
         torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0 and K > 0:
+        sys.stderr.write("bench.py: --dump-outputs %s\n" % json.dumps(dump_outputs(args.dump_outputs, {"rgb": rgb, "gbuffer": comp})))
     # per-phase times from events on the stream each phase ran on (no host synchronisation inside the timed region)
     phases = dict(zip(("render", "allgather", "composite"), (v * 1e-3 for v in source.phase_ms())))
     phases["sr_strip_and_allgather"] = sum(a.elapsed_time(b) * 1e-3 if dev == "cuda" else b - a for a, b in sr_events)

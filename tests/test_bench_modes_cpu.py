@@ -90,6 +90,36 @@ def test_train_mode_one_rank_line_is_self_sufficient(tmp_path):
     assert d["allreduce"] is None and d["cpu_baseline"]["unit"] == "clips/s"
 
 
+def test_train_mode_dump_outputs_writes_the_last_steps_loss_and_weights(tmp_path):
+    d = _launch([os.path.join(ROOT, "bench.py"), "--mode", "train", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                 "--train-batch", "1", "--train-frames", "2", "--train-crop", "16", "--dump-outputs", str(tmp_path / "out")], 0, tmp_path, nproc=1)
+    loss = np.load(tmp_path / "out" / "loss.npy")
+    params = np.load(tmp_path / "out" / "parameters.npy")
+    assert loss.dtype == np.float64 and loss.shape == (1,) and loss[0] == d["loss"]
+    assert params.dtype == np.float32 and params.shape == (911046,) and np.isfinite(params).all()
+
+
+def test_dump_outputs_whole_within_the_budget_else_a_fixed_sample(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    small = torch.arange(10, dtype=torch.float16)
+    big = np.arange(1000, dtype=np.float32).reshape(10, 100)
+    wide = np.linspace(0, 1, 50, dtype=np.float64)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2000)
+    desc = bench.dump_outputs(str(tmp_path / "a"), {"big": big, "small": small, "wide": wide})
+    out = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("big", "small", "wide")}
+    assert out["small"].dtype == np.float32 and np.array_equal(out["small"], np.arange(10, dtype=np.float32))
+    assert out["wide"].dtype == np.float64 and np.array_equal(out["wide"], wide)              # 400 bytes: whole
+    assert sum(a.nbytes for a in out.values()) <= 2000
+    k = (2000 - 40 - 400) // 4                                                                   # what is left for the largest, in elements
+    assert out["big"].shape == (k,) and desc["big"].startswith("%d of the 1000 elements" % k)
+    assert np.all(np.diff(out["big"]) > 0) and set(out["big"].tolist()) <= set(big.ravel().tolist())
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big * 2, "small": small, "wide": wide})
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), out["big"] * 2)                  # the same elements on every run
+    assert not bench.parse([]).full and bench.parse([]).dump_outputs == ""
+
+
 def test_train_mode_capture_failure_falls_back_to_the_eager_step():
     """If capturing the step (with its RCCL all-reduce) fails on the driver's node, the run goes on eagerly in the same
     process and says so in the line -- never a re-exec of a process that has touched the GPU."""

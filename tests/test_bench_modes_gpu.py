@@ -42,12 +42,31 @@ def test_tiled_mode_two_ranks_on_one_gpu_composite_and_output_equal_one_rank():
 
 
 def test_default_mode_two_ranks_on_one_gpu():
-    d = _bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-fast-mode", "--no-exact-leg"], 2, 29814)
+    d = _bench(["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-fast-mode", "--no-exact-leg"], 2, 29814)
     assert d["n_gpus"] == 2 and d["ranks_joined"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["frames_per_rank"] == 6
     assert d["config"]["spin_kernel_forms"] == {"trunk_dataflow": False, "flow_fill_one": False}
     ft = d["frame_time"]
     assert ft["gap_ms_per_frame"] == pytest.approx(d["ms_per_step"] - ft["main_stream_kernels_ms_per_frame"]) and ft["host_enqueue_ms_per_frame"] > 0
+
+
+def test_plain_run_is_the_timed_region_and_dumps_the_last_frame(tmp_path):
+    """Without --full the line stops at the timed region (no leg after it); --dump-outputs writes the last timed frame's rgb and raw."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "BENCH_SHARE_DEVICE"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--volume", "sphere64",
+                          "--low", "64x48", "--dump-outputs", str(tmp_path)], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr.decode(errors="replace")[-3000:]
+    d = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert not {"sequence_start", "sustained", "exact_f32", "f16_fast_mode", "cpu_baseline", "parity"} & set(d)
+    assert d["roofline"]["achieved"] > 0 and d["frame_time"] is None
+    import numpy as np
+    rgb, raw = np.load(tmp_path / "rgb.npy"), np.load(tmp_path / "raw.npy")
+    assert rgb.dtype == raw.dtype == np.float32 and rgb.shape == (1, 3, 192, 256) and raw.shape == (1, 6, 192, 256)
+    assert np.isfinite(rgb).all() and np.isfinite(raw).all()
 
 
 def test_train_mode_on_the_gpu_reports_clips_per_rank():
