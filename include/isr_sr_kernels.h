@@ -232,6 +232,16 @@ int isrAssembleInputRect(const float* gbuffer_hwc12, const float* flow_filled, c
 int isrAssembleInputPacked(const float* gbuffer_hwc12, const float* flow_filled, const float* prev_high, float* net_input,
                            int h, int w, int init_mode, int ao_inverted, void* trunk_workspace, void* stream);
 
+/* Input assembly of one frame of a COLOUR network (RGB in, RGB out; SuperresolutionNetwork/inference/loadedmodel.py:97-118), one launch:
+ *   net_input[variant + 48][h][w] = cat(selection of the G-buffer, flatten_high(warp_upscale(prev_high3, flow, 4, special_mask=False), 4))
+ * variant = number of selected channels: 8 clamp(r g b mask nx ny nz depth, 0, 1); 7 r g b mask nx ny nz; 5 r g b mask depth; 4 r g b mask.
+ * prev_high3: [3][4h][4w] (the previous frame's clamped output) or NULL; then init_mode 0 gives zeros and init_mode 2 the x4 bilinear
+ * resize of the selection's first three planes, which is warped by the flow like any previous image (so flow_filled is needed on the
+ * first frame as well).  init_mode 1 ("unshaded") does not exist for three channels: -1.  The warp's arithmetic is isrAssembleInput's
+ * (all three channels zero-padded, no mask remap): bit-identical to models/videotools.py. */
+int isrAssembleInputColour(const float* gbuffer_hwc12, const float* flow_filled, const float* prev_high3, float* net_input,
+                           int h, int w, int variant, int init_mode, void* stream);
+
 /* Hole filling of the low-res flow (channels 8,9 of the HWC G-buffer) where the mask (channel 3) is 0:
  * mask-weighted push-pull pyramid, the on-device replacement of the reference's CPU OpenCV
  * cv.inpaint call (inference/loadedmodel.py:77-82).  flow_out: [2][h][w].  Three launches. */
@@ -266,6 +276,14 @@ int isrFinishFrame(const float* raw, const float* net_input, float* next_prev, f
 int isrConvSmallFinishFrame(const float* x, const float* w8, const float* bias8, const float* net_input, float* next_prev, float* rgb,
                             int Cin, int h, int w, long long xPlane, const float* shading24, int exponent, float ao_strength,
                             int inverse_ao, int enable_specular, void* stream);
+
+/* End of one frame of a COLOUR network: out3[c] = clamp(raw3[c] + bilinear x4 of net_input[c], 0, 1), c = 0 .. 2 -- the arithmetic of
+ * isrReconResidualForward (k = 3), then the clamp of mainVideo.py:416.  out3 [3][4h][4w] is the displayed RGB and the next frame's
+ * previous image.  isrConvSmallFinishFrameColour: the same behind the last layer (64 -> 3, w8 / bias8 from isrConvSmallPrepare with
+ * Cout = 3) in one launch, as isrConvSmallFinishFrame. */
+int isrFinishFrameColour(const float* raw3, const float* net_input, float* out3, int h, int w, void* stream);
+int isrConvSmallFinishFrameColour(const float* x, const float* w8, const float* bias8, const float* net_input, float* out3,
+                                  int Cin, int h, int w, long long xPlane, void* stream);
 
 /* isrConv3x3ForwardSplit for one image whose result is written PACKED-SPLIT instead of fp32: every output value already as
  * the (hi, lo') fp16 pair the next split-operand layer multiplies, eight channels of a pixel per 16-byte unit,
@@ -361,6 +379,19 @@ int isrConvTailFinishFramePacked(const void* xps, const void* wq6, const float* 
                                  const float* net_input, float* next_prev, float* rgb, int h, int w, long long xpsPlane,
                                  const float* shading24, int exponent, float ao_strength, int inverse_ao, int enable_specular, void* stream);
 
+/* The tail of a COLOUR network (postblock.8 is 64 -> 3): the same two launches with THREE output channels -- 27 tap-partial rows (one
+ * 32-row block of the extra product instead of two), nine S planes and end-pixel records of 54 floats instead of eighteen and 108; the
+ * same split-operand arithmetic and the same fixed order of additions, ((bias + S0) + S1) + S2 with (z0 + z1) + z2 per row, so every
+ * pixel is independent of where tile borders fall.  The finishing is isrFinishFrameColour's: out3 [3][4h][4w].
+ *   wz: isrConvTailPrepare3(w8 [3][64][3][3]) into isrConvTailWeightBytes() bytes; bias8 [3]; workspace: isrConvTailWorkspaceBytes3(h, w);
+ *   isrConvTailSupported says whether the tensors qualify, as for six channels. */
+long long isrConvTailWorkspaceBytes3(int h, int w);
+int isrConvTailPrepare3(const float* w8, void* wz, void* stream);
+int isrConvTailFinishFrame3(const float* x, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
+                            const float* net_input, float* out3, int h, int w, long long xPlane, void* stream);
+int isrConvTailFinishFrame3Packed(const void* xps, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
+                                  const float* net_input, float* out3, int h, int w, long long xpsPlane, void* stream);
+
 /* PHASE-DECOMPOSED x2-upsampling convolution (csrc/sr_conv_upsp.h): y = act(conv3x3(U2(x), w) + bias) for EnhanceNet's two
  * upsampling layers (SuperresolutionNetwork/models/enhancenet.py:113-124: nn.Upsample(scale_factor=2, mode='bilinear') + Conv2d(64, 64, 3)),
  * 64 -> 64 channels, one image, input and output PACKED-SPLIT (the layout of isrConv3x3ForwardSplitPacked: [2 parts][8 groups][plane
@@ -393,7 +424,7 @@ void isrSetTrunkRows(int rows);
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels
- * (input assembly, trunk input packing, flow fill, tail finishing: variants 25-29, zero flops).  After synchronising the
+ * (input assembly, trunk input packing, flow fill, tail finishing: variants 25-30 and the colour networks' 34-36, zero flops).  After synchronising the
  * stream, record i gives variant = 2*MT + upsample (MT = 1|2 M tiles of 32 output channels), the
  * algorithmic FLOPs 2*9*Cin*Cout*N*H*W of the dispatch and its duration in ms. */
 int isrProfileEnable(int on);

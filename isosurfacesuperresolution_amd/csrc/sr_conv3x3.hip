@@ -1699,7 +1699,7 @@ static hipEvent_t pool_event()
 
 void isr_profile_record(int variant, double flops, hipEvent_t* e0, hipEvent_t* e1)
 {
-    if (!g_profile || (variant >= ISR_VARIANT_TRUNK_PACK && variant <= ISR_VARIANT_UPS_FRAME && !g_profile_small)) return;
+    if (!g_profile || (isr_variant_is_small(variant) && !g_profile_small)) return;
     *e0 = pool_event(); *e1 = pool_event();
     g_records.push_back({ variant, flops, *e0, *e1 });
 }
@@ -2116,6 +2116,8 @@ struct SmallConvParams {
     FinishParams fin;
 };
 
+// COLOUR (with p.finish): the frame of a colour network -- three output channels, isr_finish_pixel_colour (isrConvSmallFinishFrameColour)
+template <bool COLOUR>
 __global__ __launch_bounds__(256, 2) void conv3x3_small_cout_kernel(const SmallConvParams p)
 {
     __shared__ __attribute__((aligned(16))) float patch[2][SM_PBUF];
@@ -2223,10 +2225,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_small_cout_kernel(const SmallC
             for (int r = 0; r < 4; ++r) {
                 const int oy = oy0 + 4 * wave + r;
                 if (oy >= p.H) break;
-                float v[6];
+                if constexpr (COLOUR) {
+                    float v[3];
 #pragma unroll
-                for (int co = 0; co < 6; ++co) v[co] = acc[co >> 2][r][co & 3] + p.bias8[co];
-                isr_finish_pixel(p.fin, ox, oy, v);
+                    for (int co = 0; co < 3; ++co) v[co] = acc[0][r][co] + p.bias8[co];
+                    isr_finish_pixel_colour(p.fin, ox, oy, v);
+                } else {
+                    float v[6];
+#pragma unroll
+                    for (int co = 0; co < 6; ++co) v[co] = acc[co >> 2][r][co & 3] + p.bias8[co];
+                    isr_finish_pixel(p.fin, ox, oy, v);
+                }
             }
         }
         return;
@@ -2314,7 +2323,7 @@ int isrConv3x3SmallCoutStrided(const float* x, const float* w8, const float* bia
         e0 = pool_event(); e1 = pool_event();
         g_records.push_back({ 6, 2.0 * 9 * Cin * Cout * (double)N * H * W, e0, e1 });
     }
-    ISR_LAUNCH(conv3x3_small_cout_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
+    ISR_LAUNCH(conv3x3_small_cout_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2338,7 +2347,30 @@ int isrConvSmallFinishFrame(const float* x, const float* w8, const float* bias8,
         e0 = pool_event(); e1 = pool_event();
         g_records.push_back({ 6, 2.0 * 9 * Cin * 6 * (double)H * W, e0, e1 });
     }
-    ISR_LAUNCH(conv3x3_small_cout_kernel, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
+    ISR_LAUNCH(conv3x3_small_cout_kernel<false>, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrConvSmallFinishFrameColour(const float* x, const float* w8, const float* bias8, const float* net_input, float* out3,
+                                  int Cin, int h, int w, long long xPlane, void* stream)
+{
+    if (!x || !w8 || !bias8 || !net_input || !out3 || Cin <= 0 || h <= 0 || w <= 0) return -1;
+    const int H = 4 * h, W = 4 * w;
+    if (xPlane < (long long)H * W || (long long)Cin * xPlane * 4 >= (1LL << 31)) return -1;
+    SmallConvParams p;
+    p.x = x; p.wq = w8; p.bias8 = bias8; p.residual = nullptr; p.y = nullptr;
+    p.N = 1; p.Cin = Cin; p.H = H; p.W = W; p.Cout = 3;
+    p.tilesX = (W + SM_TW - 1) / SM_TW; p.tilesY = (H + SM_TH - 1) / SM_TH;
+    p.act = ISR_ACT_NONE; p.slope = 0.f;
+    p.xPlane = xPlane; p.xImage = (long long)Cin * xPlane;
+    p.finish = 1;
+    isr_fill_finish_params(p.fin, nullptr, net_input, out3, nullptr, h, w, nullptr, 1, 0.f, 0, 0);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (g_profile) {
+        e0 = pool_event(); e1 = pool_event();
+        g_records.push_back({ 6, 2.0 * 9 * Cin * 3 * (double)H * W, e0, e1 });
+    }
+    ISR_LAUNCH(conv3x3_small_cout_kernel<true>, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -52,7 +52,19 @@ struct TailParams {
 __host__ __device__ __forceinline__ constexpr int tail_zrow(int t, int c) { return (t % 3) * 18 + (t / 3) * 6 + c; }
 constexpr int TS_GROUPS = 18;                                                // (dy, c) pairs: the planes of the S form
 constexpr int TS_STRIDE = ST_W + 2;                                          // slab row: pixels -1 .. 32 of the wave's row (the two pad columns are zero)
-constexpr int TS_REC = 6 * TS_GROUPS;                                        // floats of one (image row, tile) edge record: kinds A .. F x 18 groups
+[[maybe_unused]] constexpr int TS_REC = 6 * TS_GROUPS;                                        // floats of one (image row, tile) edge record: kinds A .. F x 18 groups
+// The S form for CO output channels (6: the unshaded networks; 3: the colour networks, RGB out) -- everything above with 6 replaced by
+// a compile-time CO: 9 CO z rows (27: ONE 32-row block of the z product instead of two), 3 CO S planes, records of 6 x 3 CO floats.
+// The six-channel instantiation is the code it was before the parameter existed.
+template <int CO> struct TailShape {
+    static_assert(CO == 6 || CO == 3, "the last layer has six (unshaded) or three (colour) output channels");
+    static constexpr int ZROWS = 9 * CO;                                     // 54 | 27
+    static constexpr int GROUPS = 3 * CO;                                    // 18 | 9  (dy, c) pairs
+    static constexpr int REC = 6 * GROUPS;                                   // 108 | 54
+    static constexpr int MBLOCKS = (ZROWS + 31) / 32;                        // 2 | 1  32-row blocks of the z product
+    static constexpr int GHALF = (GROUPS + 1) / 2;                           // 9 | 5  groups a lane half adds
+};
+template <int CO> __host__ __device__ __forceinline__ constexpr int tail_zrow_co(int t, int c) { return (t % 3) * (3 * CO) + (t / 3) * CO + c; }
 
 __device__ __forceinline__ bool tail_in_image(int x, int y, int W, int H) { return (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H; }
 
@@ -86,9 +98,11 @@ constexpr int ZW_OFF = S_WUNITS - TZ_UNITS;                                  // 
 // pad columns are zero) and stores 18 S planes instead of 54 z planes; the two pixels at the row's ends, whose sums need a value
 // of the neighbouring tile, get their three addends from small per-(row, tile) records and are added -- in the SAME order
 // (z[dx=0] + z[dx=1]) + z[dx=2] -- by the finishing kernel: every pixel's arithmetic is independent of where tile borders fall.
-template <int FORM, bool PSIN>
+template <int FORM, bool PSIN, int CO = 6>
 __global__ __launch_bounds__(S_THREADS, 2) void conv3x3_split_tail_kernel(const TailParams tp)
 {
+    static_assert(CO == 6 || FORM == 2, "three output channels: the S form only");
+    using TSH = TailShape<CO>;
     constexpr bool FUSED = FORM == 1;
     constexpr bool SFORM = FORM == 2 || FORM == 4;                           // horizontal tap sums through the wave's slab (4: + the vertical sums of the tile's inner rows)
     const SplitConvParams& p = tp.c;
@@ -220,8 +234,8 @@ __global__ __launch_bounds__(S_THREADS, 2) void conv3x3_split_tail_kernel(const 
     const float zunscale = reinterpret_cast<const float*>(tp.wz)[1];
     float* bias_lds = reinterpret_cast<float*>(wbuf + S_WUNITS);
     if (tid < 64) bias_lds[tid] = p.bias ? p.bias[tid] : 0.0f;
-    const rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(tp.z, 0, (int)((size_t)(SFORM ? TS_GROUPS : TZ_ROWS) * tp.zPlane * 4), 0x00020000);
-    const rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(tp.srec, 0, SFORM ? (int)((size_t)p.H * p.tilesX * TS_REC * 4) : 0, 0x00020000);
+    const rsrc_t zrs = __builtin_amdgcn_make_buffer_rsrc(tp.z, 0, (int)((size_t)(SFORM ? TSH::GROUPS : TZ_ROWS) * tp.zPlane * 4), 0x00020000);
+    const rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(tp.srec, 0, SFORM ? (int)((size_t)p.H * p.tilesX * TSH::REC * 4) : 0, 0x00020000);
     u32x4 zw[4];                                                             // this thread's 4 of the 1024 units of the z weights
 
     Tile cur = decode(jw);
@@ -294,7 +308,7 @@ __global__ __launch_bounds__(S_THREADS, 2) void conv3x3_split_tail_kernel(const 
             }
             const int oy = cur.oy0 + wave * 2 + r;
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
+            for (int mb = 0; mb < TSH::MBLOCKS; ++mb) {
                 f32x16 zacc;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) zacc[i] = 0.0f;
@@ -319,7 +333,7 @@ __global__ __launch_bounds__(S_THREADS, 2) void conv3x3_split_tail_kernel(const 
                     const float zs = (cur.ox0 + j < p.W) ? zunscale : 0.0f; // a pixel beyond the image's right edge contributes nothing to its neighbour
 #pragma unroll
                     for (int i = 0; i < 16; ++i)
-                        if (mb == 0 || (i >> 2) < 3) tr[(mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * TS_STRIDE + j + 1] = zacc[i] * zs;
+                        if (CO == 6 ? (mb == 0 || (i >> 2) < 3) : ((i >> 2) < 3 || h == 0)) tr[(mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * TS_STRIDE + j + 1] = zacc[i] * zs;
                 } else {                                                     // ... into this wave's transposition slab
 #pragma unroll
                     for (int i = 0; i < 16; ++i) tr[(mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * 32 + j] = zacc[i] * zunscale;
@@ -327,29 +341,32 @@ __global__ __launch_bounds__(S_THREADS, 2) void conv3x3_split_tail_kernel(const 
             }
             if (FUSED) continue;
             if (SFORM) {
-                if (lane < TZ_ROWS) { tr[lane * TS_STRIDE] = 0.0f; tr[lane * TS_STRIDE + TS_STRIDE - 1] = 0.0f; }      // the pad columns
+                if (lane < TSH::ZROWS) { tr[lane * TS_STRIDE] = 0.0f; tr[lane * TS_STRIDE + TS_STRIDE - 1] = 0.0f; }      // the pad columns
                 __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0): same-wave hand-off through LDS
-                // lane (j, h) adds groups g = 9 h + k, k = 0 .. 8: S[g][pixel j] = (z[dx 0][j - 1] + z[dx 1][j]) + z[dx 2][j + 1]
-                const float* sb = tr + (9 * h) * TS_STRIDE + j;
+                // lane (j, h) adds groups g = 9 h + k, k = 0 .. 8 (three channels: 5 h + k, k = 0 .. 4, g < 9):
+                // S[g][pixel j] = (z[dx 0][j - 1] + z[dx 1][j]) + z[dx 2][j + 1]
+                const float* sb = tr + (TSH::GHALF * h) * TS_STRIDE + j;
                 const bool live = oy < p.H && cur.ox0 + j < p.W;
-                const unsigned sv = live ? ((unsigned)(9 * h) * (unsigned)tp.zPlane + (unsigned)(oy * p.W + cur.ox0 + j)) * 4u : BAD_OFFSET;
+                const unsigned sv = live ? ((unsigned)(TSH::GHALF * h) * (unsigned)tp.zPlane + (unsigned)(oy * p.W + cur.ox0 + j)) * 4u : BAD_OFFSET;
 #pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    const float sum = (sb[k * TS_STRIDE] + sb[(TS_GROUPS + k) * TS_STRIDE + 1]) + sb[(2 * TS_GROUPS + k) * TS_STRIDE + 2];
-                    if (FORM == 4) sreg[r][k] = sum;                         // V form: kept for the vertical sums below
-                    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sum), zrs, (int)sv, k * tp.zPlane * 4, 0);
+                for (int k = 0; k < TSH::GHALF; ++k) {
+                    const float sum = (sb[k * TS_STRIDE] + sb[(TSH::GROUPS + k) * TS_STRIDE + 1]) + sb[(2 * TSH::GROUPS + k) * TS_STRIDE + 2];
+                    // (an odd number of groups: the upper half's last slot is no group -- it reads slab rows that exist and stores nothing)
+                    const unsigned svk = (TSH::GROUPS % 2 == 0 || TSH::GHALF * h + k < TSH::GROUPS) ? sv : BAD_OFFSET;
+                    if (FORM == 4) sreg[r][k] = sum;             // V form: kept for the vertical sums below
+                    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sum), zrs, (int)svk, k * tp.zPlane * 4, 0);
                 }
                 // the addends of the two end pixels (and of the neighbours' end pixels), 6 x 18 floats per (row, tile):
                 //   A z[dx 0] @ 30, B z[dx 1] @ 31, C z[dx 0] @ 31, D z[dx 1] @ 0, E z[dx 2] @ 1, F z[dx 2] @ 0   (pixel of this row)
 #pragma unroll
-                for (int rr = 0; rr < 2; ++rr) {
+                for (int rr = 0; rr < (TSH::REC + 63) / 64; ++rr) {
                     const int idx = lane + 64 * rr;
-                    const int kind = idx / TS_GROUPS, g = idx - kind * TS_GROUPS;
+                    const int kind = idx / TSH::GROUPS, g = idx - kind * TSH::GROUPS;
                     const int zdx = kind == 0 || kind == 2 ? 0 : (kind == 1 || kind == 3 ? 1 : 2);
                     const int col = kind == 0 ? 31 : (kind == 1 || kind == 2) ? 32 : (kind == 4 ? 2 : 1);        // slab column = pixel + 1
-                    const float val = idx < TS_REC ? tr[(zdx * TS_GROUPS + g) * TS_STRIDE + col] : 0.0f;
+                    const float val = idx < TSH::REC ? tr[(zdx * TSH::GROUPS + g) * TS_STRIDE + col] : 0.0f;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), rrs,
-                                                          (int)((idx < TS_REC && oy < p.H) ? ((unsigned)(oy * p.tilesX + cur.ox0 / ST_W) * TS_REC + (unsigned)idx) * 4u : BAD_OFFSET), 0, 0);
+                                                          (int)((idx < TSH::REC && oy < p.H) ? ((unsigned)(oy * p.tilesX + cur.ox0 / ST_W) * TSH::REC + (unsigned)idx) * 4u : BAD_OFFSET), 0, 0);
                 }
                 __builtin_amdgcn_s_waitcnt(0xC07F);                          // reads done before the next row overwrites the slab
                 continue;
@@ -530,15 +547,17 @@ struct TailSFinishParams {
     const float* bias8;
 };
 
+template <int CO>
 __global__ __launch_bounds__(256) void tail_s_finish_kernel(const TailSFinishParams p)
 {
+    constexpr int TS_GROUPS = TailShape<CO>::GROUPS, TS_REC = TailShape<CO>::REC;       // (shadow the six-channel constants)
     __shared__ float sedge[16][TS_GROUPS + 1];
     const int H = 4 * p.fin.h, W = 4 * p.fin.w;
     const int X0 = blockIdx.x * 256, Y = blockIdx.y, tid = threadIdx.x;
     for (int t = tid; t < 16 * TS_GROUPS; t += 256) {
         const int ep = t / TS_GROUPS, g = t - ep * TS_GROUPS;
         const int tile = X0 / ST_W + (ep >> 1), side = ep & 1;
-        const int py = Y + g / 6 - 1, X = tile * ST_W + side * (ST_W - 1);
+        const int py = Y + g / CO - 1, X = tile * ST_W + side * (ST_W - 1);
         float val = 0.0f;
         if (tile < p.tilesX && X < W && (unsigned)py < (unsigned)H) {
             const float* own = p.rec + ((size_t)py * p.tilesX + tile) * TS_REC + g;
@@ -560,26 +579,27 @@ __global__ __launch_bounds__(256) void tail_s_finish_kernel(const TailSFinishPar
     const int j = X & (ST_W - 1);
     const bool edge = j == 0 || j == ST_W - 1;
     const int ep = (tid >> 5) * 2 + (j == ST_W - 1 ? 1 : 0);
-    float v[6];
+    float v[CO];
 #pragma unroll
-    for (int c = 0; c < 6; ++c) v[c] = p.bias8[c];
+    for (int c = 0; c < CO; ++c) v[c] = p.bias8[c];
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
         const int py = Y + dy - 1;
         if ((unsigned)py < (unsigned)H) {
-            const float* sp = p.s + (size_t)(dy * 6) * p.zPlane + (size_t)py * W + X;
-            float sv[6];
+            const float* sp = p.s + (size_t)(dy * CO) * p.zPlane + (size_t)py * W + X;
+            float sv[CO];
 #pragma unroll
-            for (int c = 0; c < 6; ++c) sv[c] = sp[(size_t)c * p.zPlane];
+            for (int c = 0; c < CO; ++c) sv[c] = sp[(size_t)c * p.zPlane];
             if (edge) {
 #pragma unroll
-                for (int c = 0; c < 6; ++c) sv[c] = sedge[ep][dy * 6 + c];
+                for (int c = 0; c < CO; ++c) sv[c] = sedge[ep][dy * CO + c];
             }
 #pragma unroll
-            for (int c = 0; c < 6; ++c) v[c] += sv[c];
+            for (int c = 0; c < CO; ++c) v[c] += sv[c];
         }
     }
-    isr_finish_pixel(p.fin, X, Y, v);
+    if constexpr (CO == 6) isr_finish_pixel(p.fin, X, Y, v);
+    else isr_finish_pixel_colour(p.fin, X, Y, v);
 }
 
 #ifdef ISR_DIAG      // (form 4's second launch: the diagnostics build only)
@@ -695,11 +715,13 @@ __global__ __launch_bounds__(256) void tail_seam_finish_kernel(const TailParams 
 
 // w8 [6][64][3][3] fp32 -> header + [q][part][h][m] units: element e of (q, h) is y6 channel 32 (q >> 1) + 16 (q & 1) + (e & 3) +
 // 8 (e >> 2) + 4 h, row m = tail_zrow(t, c) holds w8[c][.][t] 2^S (rows >= 54 zero); part 0 = hi, 1 = lo
+template <int CO>
 __global__ __launch_bounds__(256) void tail_prepare_kernel(const float* __restrict__ w8, u32x4* __restrict__ wz)
 {
+    using TSH = TailShape<CO>;
     __shared__ float red[256];
     float m = 0.0f;
-    for (int i = threadIdx.x; i < 6 * 64 * 9; i += 256) m = fmaxf(m, fabsf(w8[i]));
+    for (int i = threadIdx.x; i < CO * 64 * 9; i += 256) m = fmaxf(m, fabsf(w8[i]));
     red[threadIdx.x] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -722,14 +744,14 @@ __global__ __launch_bounds__(256) void tail_prepare_kernel(const float* __restri
     }
     for (int u = threadIdx.x; u < 4 * 2 * 64; u += 256) {                     // (q, h, m)
         const int mrow = u & 63, hh = (u >> 6) & 1, q = u >> 7;
-        const int dxr = mrow / 18, gr = mrow - dxr * 18;                      // row [dx][dy][c] (tail_zrow)
-        const int t = 3 * (gr / 6) + dxr, c = gr % 6;
+        const int dxr = mrow / TSH::GROUPS, gr = mrow - dxr * TSH::GROUPS;    // row [dx][dy][c] (tail_zrow)
+        const int t = 3 * (gr / CO) + dxr, c = gr % CO;
         f16x8 qh, ql;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int k = 32 * (q >> 1) + 16 * (q & 1) + (e & 3) + 8 * (e >> 2) + 4 * hh;
             _Float16 a, b;
-            split16(mrow < TZ_ROWS ? w8[((size_t)c * 64 + k) * 9 + t] * scale : 0.0f, a, b);
+            split16(mrow < TSH::ZROWS ? w8[((size_t)c * 64 + k) * 9 + t] * scale : 0.0f, a, b);
             qh[e] = a; ql[e] = b;
         }
         wz[1 + ((q * 2 + 0) * 2 + hh) * 64 + mrow] = __builtin_bit_cast(u32x4, qh);
@@ -771,8 +793,24 @@ long long isrConvTailWorkspaceBytes(int h, int w)
 int isrConvTailPrepare(const float* w8, void* wz, void* stream)
 {
     if (!w8 || !wz) return -1;
-    hipLaunchKernelGGL(tail_prepare_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, w8, (u32x4*)wz);
+    hipLaunchKernelGGL(tail_prepare_kernel<6>, dim3(1), dim3(256), 0, (hipStream_t)stream, w8, (u32x4*)wz);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+/* ... for a colour network's last layer, w8 [3][64][3][3]: the same image size (isrConvTailWeightBytes), rows >= 27 zero */
+int isrConvTailPrepare3(const float* w8, void* wz, void* stream)
+{
+    if (!w8 || !wz) return -1;
+    hipLaunchKernelGGL(tail_prepare_kernel<3>, dim3(1), dim3(256), 0, (hipStream_t)stream, w8, (u32x4*)wz);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+/* nine S planes + the end-pixel records [4h][tiles][6][9] */
+long long isrConvTailWorkspaceBytes3(int h, int w)
+{
+    if (h <= 0 || w <= 0) return -1;
+    const long long H = 4LL * h, W = 4LL * w;
+    return ((long long)TailShape<3>::GROUPS * (H * W + W) + H * ((W + ST_W - 1) / ST_W) * TailShape<3>::REC) * 4;
 }
 
 int isrConvTailSupported(const float* x, int h, int w, long long xPlane)
@@ -784,7 +822,7 @@ int isrConvTailSupported(const float* x, int h, int w, long long xPlane)
     return 1;
 }
 
-static int tail_launch(const void* x, int packed, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
+static int tail_launch(int co, const void* x, int packed, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
                        const float* net_input, float* next_prev, float* rgb, int h, int w, long long xPlane,
                        const float* shading24, int exponent, float ao_strength, int inverse_ao, int enable_specular, void* stream);
 
@@ -792,7 +830,7 @@ int isrConvTailFinishFrame(const float* x, const void* wq6, const float* bias6, 
                            const float* net_input, float* next_prev, float* rgb, int h, int w, long long xPlane,
                            const float* shading24, int exponent, float ao_strength, int inverse_ao, int enable_specular, void* stream)
 {
-    return tail_launch(x, 0, wq6, bias6, wz, bias8, workspace, net_input, next_prev, rgb, h, w, xPlane, shading24, exponent, ao_strength,
+    return tail_launch(6, x, 0, wq6, bias6, wz, bias8, workspace, net_input, next_prev, rgb, h, w, xPlane, shading24, exponent, ao_strength,
                        inverse_ao, enable_specular, stream);
 }
 
@@ -800,17 +838,32 @@ int isrConvTailFinishFramePacked(const void* xps, const void* wq6, const float* 
                                  const float* net_input, float* next_prev, float* rgb, int h, int w, long long xpsPlane,
                                  const float* shading24, int exponent, float ao_strength, int inverse_ao, int enable_specular, void* stream)
 {
-    return tail_launch(xps, 1, wq6, bias6, wz, bias8, workspace, net_input, next_prev, rgb, h, w, xpsPlane, shading24, exponent, ao_strength,
+    return tail_launch(6, xps, 1, wq6, bias6, wz, bias8, workspace, net_input, next_prev, rgb, h, w, xpsPlane, shading24, exponent, ao_strength,
                        inverse_ao, enable_specular, stream);
 }
 
-static int tail_launch(const void* xin, int packed, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
+/* The colour networks' tail (RGB out): postblock.6 + ReLU, postblock.8 (64 -> 3) as nine tap products, the S-form combine and
+ * isr_finish_pixel_colour -- out3 [3][4h][4w] = clamp(conv + bilinear x4 of net_input[0..2], 0, 1), the displayed RGB and the next
+ * frame's previous image.  wz: isrConvTailPrepare3; workspace: isrConvTailWorkspaceBytes3; otherwise as isrConvTailFinishFrame. */
+int isrConvTailFinishFrame3(const float* x, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
+                            const float* net_input, float* out3, int h, int w, long long xPlane, void* stream)
+{
+    return tail_launch(3, x, 0, wq6, bias6, wz, bias8, workspace, net_input, out3, nullptr, h, w, xPlane, nullptr, 1, 0.f, 0, 0, stream);
+}
+
+int isrConvTailFinishFrame3Packed(const void* xps, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
+                                  const float* net_input, float* out3, int h, int w, long long xpsPlane, void* stream)
+{
+    return tail_launch(3, xps, 1, wq6, bias6, wz, bias8, workspace, net_input, out3, nullptr, h, w, xpsPlane, nullptr, 1, 0.f, 0, 0, stream);
+}
+
+static int tail_launch(int co, const void* xin, int packed, const void* wq6, const float* bias6, const void* wz, const float* bias8, void* workspace,
                        const float* net_input, float* next_prev, float* rgb, int h, int w, long long xPlane,
                        const float* shading24, int exponent, float ao_strength, int inverse_ao, int enable_specular, void* stream)
 {
     const float* x = (const float*)xin;
     unsigned* const rangeFlag = isr_take_range_flag();       // taken first: an error return must not leave it armed
-    if (!x || !wq6 || !wz || !bias8 || !workspace || !net_input || !next_prev || (rgb && !shading24)) return -1;
+    if (!x || !wq6 || !wz || !bias8 || !workspace || !net_input || !next_prev || (rgb && !shading24) || (co != 6 && co != 3)) return -1;
     if (!packed && !isrConvTailSupported(x, h, w, xPlane)) return -3;
     const int H = 4 * h, W = 4 * w;
     if (packed && (((uintptr_t)xin & 15) != 0 || xPlane < (long long)H * W || xPlane * 16 * 16 > 0x7fffffffLL
@@ -851,6 +904,8 @@ static int tail_launch(const void* xin, int packed, const void* wq6, const float
 #endif
         (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
         (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
 #ifdef ISR_DIAG
         (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
         (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
@@ -866,9 +921,24 @@ static int tail_launch(const void* xin, int packed, const void* wq6, const float
     tp.colrec = tp.rowrec + tail_row_floats(H, W);
     const bool fused = g_tail_fused == 1 && !packed;
     // algorithmic flops: postblock.6 and the final 64 -> 6 layer, whose arithmetic this launch carries
-    isr_profile_record(ISR_VARIANT_SPLIT_TAIL, 2.0 * 9 * 64 * (64 + 6) * (double)H * W, &e0, &e1);
-    tp.srec = tp.z + (size_t)TS_GROUPS * tp.zPlane;
+    isr_profile_record(co == 3 ? ISR_VARIANT_SPLIT_TAIL_COLOUR : ISR_VARIANT_SPLIT_TAIL, 2.0 * 9 * 64 * (64 + co) * (double)H * W, &e0, &e1);
+    tp.srec = tp.z + (size_t)(co == 3 ? TailShape<3>::GROUPS : TS_GROUPS) * tp.zPlane;
     const dim3 tgrid((unsigned)want), tblock(S_THREADS);
+    if (co == 3) {
+        // three output channels: the S form, in the product and in the diagnostics build alike (the other forms are six-channel experiments)
+        TailSFinishParams fp;
+        fp.fin = tp.fin;
+        fp.s = tp.z; fp.rec = tp.srec; fp.zPlane = tp.zPlane; fp.tilesX = p.tilesX; fp.bias8 = bias8;
+        if (e0 || e1) {
+            if (packed) hipExtLaunchKernelGGL((conv3x3_split_tail_kernel<2, true, 3>), tgrid, tblock, T_LDS_BYTES, s, e0, e1, 0, tp);
+            else hipExtLaunchKernelGGL((conv3x3_split_tail_kernel<2, false, 3>), tgrid, tblock, T_LDS_BYTES, s, e0, e1, 0, tp);
+        } else {
+            if (packed) hipLaunchKernelGGL((conv3x3_split_tail_kernel<2, true, 3>), tgrid, tblock, T_LDS_BYTES, s, tp);
+            else hipLaunchKernelGGL((conv3x3_split_tail_kernel<2, false, 3>), tgrid, tblock, T_LDS_BYTES, s, tp);
+        }
+        ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH_COLOUR, tail_s_finish_kernel<3>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
 #define TAIL_LAUNCH(FORM, PS)                                                                                                          \
     do {                                                                                                                               \
         if (e0 || e1) hipExtLaunchKernelGGL((conv3x3_split_tail_kernel<FORM, PS>), tgrid, tblock, T_LDS_BYTES, s, e0, e1, 0, tp);      \
@@ -888,7 +958,7 @@ static int tail_launch(const void* xin, int packed, const void* wq6, const float
             ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_v_finish_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
         } else {
             if (packed) TAIL_LAUNCH(2, true); else TAIL_LAUNCH(2, false);
-            ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_s_finish_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
+            ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_s_finish_kernel<6>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
         }
     } else {
         if (packed) TAIL_LAUNCH(0, true); else TAIL_LAUNCH(0, false);
@@ -904,7 +974,7 @@ static int tail_launch(const void* xin, int packed, const void* wq6, const float
         fp.fin = tp.fin;
         fp.s = tp.z; fp.rec = tp.srec; fp.zPlane = tp.zPlane; fp.tilesX = p.tilesX; fp.bias8 = bias8;
         if (packed) TAIL_LAUNCH(2, true); else TAIL_LAUNCH(2, false);
-        ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_s_finish_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
+        ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_s_finish_kernel<6>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
     }
 #endif
 #undef TAIL_LAUNCH

@@ -75,6 +75,40 @@ __device__ __forceinline__ void isr_finish_pixel(const FinishParams& p, int X, i
     }
 }
 
+// The x4 bilinear blend of the residual reconstruction, hy (hx a + lx b) + ly (hx c + lx d), with its multiply-adds spelled out: the
+// order recon_residual_fwd_kernel (sr_train.hip) has always evaluated it in.  Every kernel that must reproduce ops.recon_residual bit
+// for bit (the colour networks' finishing, below) goes through this one definition instead of leaving the contraction to the compiler.
+__device__ __forceinline__ float isr_recon_blend(float hy, float hx, float ly, float lx, float a, float b, float c, float d)
+{
+#pragma clang fp contract(off)
+    const float top = __builtin_fmaf(lx, b, hx * a);
+    const float bot = __builtin_fmaf(hx, c, lx * d);
+    const float u0 = hy * top, u1 = ly * bot;
+    return u0 + u1;
+}
+
+// End of a frame of a COLOUR network (RGB in, RGB out; inference/loadedmodel.py, the colour branch), per high-resolution pixel:
+// out[c] = clamp(v[c] + bilinear x4 of net_in[c], 0, 1), c = 0 .. 2 -- EnhanceNet._recon_image over channel_mask [0, 1, 2] as
+// isrReconResidualForward computes it, then the clamp of mainVideo.py:416.  Written once: p.next_prev [3][H][W] is the displayed RGB and
+// the next frame's previous image.  v[0..2]: the conv output at (X, Y).
+__device__ __forceinline__ void isr_finish_pixel_colour(const FinishParams& p, int X, int Y, float (&v)[3])
+{
+#pragma clang fp contract(off)
+    const int H = 4 * p.h, W = 4 * p.w;
+    const size_t hplane = (size_t)H * W, lplane = (size_t)p.h * p.w;
+    const size_t pix = (size_t)Y * W + X;
+    int y0, y1, x0, x1; float ly, lx;
+    isr_src_index(Y, 0.25f, p.h, y0, y1, ly);
+    isr_src_index(X, 0.25f, p.w, x0, x1, lx);
+    const float hy = 1.f - ly, hx = 1.f - lx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* q = p.net_in + (size_t)c * lplane;
+        const float r = v[c] + isr_recon_blend(hy, hx, ly, lx, q[y0 * p.w + x0], q[y0 * p.w + x1], q[y1 * p.w + x0], q[y1 * p.w + x1]);
+        p.next_prev[(size_t)c * hplane + pix] = fminf(fmaxf(r, 0.f), 1.f);
+    }
+}
+
 inline void isr_fill_finish_params(FinishParams& p, const float* raw, const float* net_input, float* next_prev, float* rgb, int h, int w,
                                    const float* shading24, int exponent, float ao_strength, int inverse_ao, int enable_specular)
 {

@@ -193,6 +193,98 @@ __global__ __launch_bounds__(256) void assemble_input_kernel(const AssembleParam
     }
 }
 
+// ---- colour networks (RGB in, RGB out): inference/loadedmodel.py, the colour branch ------------------------------------------------
+//   net_input[nsel + 48][h][w] = cat(selection of the G-buffer's first eight channels,
+//                                    flatten_high(warp_upscale(prev [3][4h][4w], flow, 4, special_mask=False), 4))
+// nsel = 8: clamp(r g b mask nx ny nz depth, 0, 1); 7: r g b mask nx ny nz; 5: r g b mask depth; 4: r g b mask.  All three channels of
+// the previous image are zero-padded and none is remapped.  Without a previous image: zeros (init_mode 0), or the x4 bilinear resize of
+// the selection's first three planes (init_mode 2; VideoTools.upscale_bilinear: the seven roundings of isr_bilerp_rn), which is warped
+// like any previous image.  Same thread layout as assemble_input_kernel: one thread per (low-resolution pixel, dx), loops over dy.
+struct AssembleColourParams {
+    const float* gbuf;      // [h][w][12]
+    const float* flow;      // [2][h][w] hole-filled flow (NULL only with prev == NULL and init_mode == 0)
+    const float* prev;      // [3][4h][4w] previous output (clamped) or NULL
+    float* out;             // [nsel + 48][h][w]
+    int h, w, nsel, init_mode;
+};
+
+__device__ __forceinline__ float colour_select(const float* g, int c, int nsel)
+{
+    const float v = g[(nsel == 5 && c == 4) ? 7 : c];
+    return nsel == 8 ? fminf(fmaxf(v, 0.f), 1.f) : v;
+}
+
+// plane c (< 3) of the x4 bilinear resize of the selection at the high-resolution pixel (X, Y)
+__device__ __forceinline__ float colour_initial(const AssembleColourParams& p, int c, int X, int Y)
+{
+    int y0, y1, x0, x1; float ly, lx;
+    src_index(Y, 0.25f, p.h, y0, y1, ly);
+    src_index(X, 0.25f, p.w, x0, x1, lx);
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    return bilerp_rn(hy, hx, ly, lx, colour_select(p.gbuf + ((size_t)y0 * p.w + x0) * 12, c, p.nsel), colour_select(p.gbuf + ((size_t)y0 * p.w + x1) * 12, c, p.nsel),
+                     colour_select(p.gbuf + ((size_t)y1 * p.w + x0) * 12, c, p.nsel), colour_select(p.gbuf + ((size_t)y1 * p.w + x1) * 12, c, p.nsel));
+}
+
+__global__ __launch_bounds__(256) void assemble_input_colour_kernel(const AssembleColourParams p)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int x = t >> 2, dx = t & 3, y = blockIdx.y;
+    if (x >= p.w) return;
+    const size_t plane = (size_t)p.h * p.w;
+    const size_t pix = (size_t)y * p.w + x;
+    if (dx == 0) {
+        const float* g = p.gbuf + pix * 12;
+        for (int c = 0; c < p.nsel; ++c) p.out[c * plane + pix] = colour_select(g, c, p.nsel);
+    }
+    const int W = 4 * p.w;
+    const size_t hplane = (size_t)(4 * p.h) * W;
+    float* const op = p.out + (size_t)p.nsel * plane + pix;
+    if (!p.prev && p.init_mode == 0) {
+        for (int c = 0; c < 3; ++c)
+            for (int dy = 0; dy < 4; ++dy) op[(size_t)(c * 16 + dy * 4 + dx) * plane] = 0.0f;
+        return;
+    }
+    for (int dy = 0; dy < 4; ++dy) {
+#pragma clang fp contract(off)
+        const IsrWarpTaps wt = isr_warp_taps(p.flow, p.flow + plane, p.h, p.w, 4 * x + dx, 4 * y + dy);
+        for (int c = 0; c < 3; ++c) {
+            float v00 = 0.f, v01 = 0.f, v10 = 0.f, v11 = 0.f;
+            if (p.prev) {
+                const float* q = p.prev + (size_t)c * hplane;
+                if (wt.vy0 && wt.vx0) v00 = q[wt.b00];
+                if (wt.vy0 && wt.vx1) v01 = q[wt.b00 + 1];
+                if (wt.vy1 && wt.vx0) v10 = q[wt.b00 + W];
+                if (wt.vy1 && wt.vx1) v11 = q[wt.b00 + W + 1];
+            } else {
+                if (wt.vy0 && wt.vx0) v00 = colour_initial(p, c, wt.ix0, wt.iy0);
+                if (wt.vy0 && wt.vx1) v01 = colour_initial(p, c, wt.ix0 + 1, wt.iy0);
+                if (wt.vy1 && wt.vx0) v10 = colour_initial(p, c, wt.ix0, wt.iy0 + 1);
+                if (wt.vy1 && wt.vx1) v11 = colour_initial(p, c, wt.ix0 + 1, wt.iy0 + 1);
+            }
+            // ((v00 w00 + v01 w01) + v10 w10) + v11 w11, one rounding per operation
+            const float t00 = v00 * wt.w00, t01 = v01 * wt.w01, t10 = v10 * wt.w10, t11 = v11 * wt.w11;
+            float r = t00 + t01;
+            r = r + t10;
+            r = r + t11;
+            op[(size_t)(c * 16 + dy * 4 + dx) * plane] = r;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void finish_frame_colour_kernel(const FinishParams p)
+{
+    const int X = blockIdx.x * blockDim.x + threadIdx.x;
+    const int Y = blockIdx.y;
+    const int H = 4 * p.h, W = 4 * p.w;
+    if (X >= W) return;
+    const size_t hplane = (size_t)H * W;
+    const size_t pix = (size_t)Y * W + X;
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = p.raw[(size_t)c * hplane + pix];
+    isr_finish_pixel_colour(p, X, Y, v);
+}
+
 __global__ __launch_bounds__(256) void finish_frame_kernel(const FinishParams p)
 {
     const int X = blockIdx.x * blockDim.x + threadIdx.x;
@@ -627,6 +719,27 @@ int isrAssembleInputPacked(const float* gbuffer_hwc12, const float* flow_filled,
                          (u32x4*)(ws + off[0]), groups0, (long long)(((long long)h * w + 8) & ~7LL), (u32x4*)(ws + off[1]), (u32x4*)(ws + off[2]),
                          (unsigned*)(ws + 16), tiles };
     ISR_LAUNCH_PROFILED(ISR_VARIANT_ASSEMBLE, assemble_input_kernel<true>, dim3((4 * w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrAssembleInputColour(const float* gbuffer_hwc12, const float* flow_filled, const float* prev_high3, float* net_input,
+                           int h, int w, int variant, int init_mode, void* stream)
+{
+    if (!gbuffer_hwc12 || !net_input || h <= 0 || w <= 0) return -1;
+    if (variant != 8 && variant != 7 && variant != 5 && variant != 4) return -1;
+    if (init_mode != 0 && init_mode != 2) return -1;             // ("unshaded" constants do not exist for three channels)
+    if ((prev_high3 || init_mode == 2) && !flow_filled) return -1;
+    AssembleColourParams p = { gbuffer_hwc12, flow_filled, prev_high3, net_input, h, w, variant, init_mode };
+    ISR_LAUNCH_PROFILED(ISR_VARIANT_ASSEMBLE_COLOUR, assemble_input_colour_kernel, dim3((4 * w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrFinishFrameColour(const float* raw3, const float* net_input, float* out3, int h, int w, void* stream)
+{
+    if (!raw3 || !net_input || !out3 || h <= 0 || w <= 0) return -1;
+    FinishParams p;
+    isr_fill_finish_params(p, raw3, net_input, out3, nullptr, h, w, nullptr, 1, 0.f, 0, 0);
+    ISR_LAUNCH_PROFILED(ISR_VARIANT_FINISH_COLOUR, finish_frame_colour_kernel, dim3((4 * w + 255) / 256, 4 * h), dim3(256), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -25,6 +25,13 @@ constexpr int ISR_VARIANT_FINISH = 29;         // finish_frame_kernel (sr_frame.
 constexpr int ISR_VARIANT_UPS_FRAME = 30;      // ups_frame_kernel (sr_conv_upsp.h): the one-pixel frame of a phase-decomposed upsampling layer
 constexpr int ISR_VARIANT_WGRAD_SPLIT = 32;    // conv3x3_wgrad_split2_kernel / conv3x3_wgrad_split_kernel (sr_conv3x3.hip): the split-operand weight gradient of one 64 x 64 channel block
 constexpr int ISR_VARIANT_SPLIT_UPSP = 31;     // conv3x3_split_upsp_kernel (sr_conv_upsp.h); NOT a "small" kernel: recorded at level 1
+// the colour networks' frame kernels (inference/loadedmodel.py, the colour branch)
+constexpr int ISR_VARIANT_SPLIT_TAIL_COLOUR = 33;  // conv3x3_split_tail_kernel<2, ., 3> (sr_conv_tail.hip): recorded at level 1, like the six-channel tail
+constexpr int ISR_VARIANT_TAIL_FINISH_COLOUR = 34; // tail_s_finish_kernel<3> (sr_conv_tail.hip)             -- small kernels from here on
+constexpr int ISR_VARIANT_ASSEMBLE_COLOUR = 35;    // assemble_input_colour_kernel (sr_frame.hip)
+constexpr int ISR_VARIANT_FINISH_COLOUR = 36;      // finish_frame_colour_kernel (sr_frame.hip)
+// the frame's small kernels are recorded at profiling level 2 only (isrProfileEnable)
+constexpr bool isr_variant_is_small(int v) { return (v >= ISR_VARIANT_TRUNK_PACK && v <= ISR_VARIANT_UPS_FRAME) || (v >= ISR_VARIANT_TAIL_FINISH_COLOUR && v <= ISR_VARIANT_FINISH_COLOUR); }
 
 // Sets *e0 / *e1 to an event pair (and records the launch) when profiling is on, leaves them untouched otherwise.
 void isr_profile_record(int variant, double flops, hipEvent_t* e0, hipEvent_t* e1);

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void recon_residual_fwd_kernel(const float* __
         float v = y[((size_t)n * cout + c) * hplane + pix];
         if (c < k) {
             const float* q = x + ((size_t)n * cin + c) * lplane;
-            v += hy * (hx * q[y0 * w + x0] + lx * q[y0 * w + x1]) + ly * (hx * q[y1 * w + x0] + lx * q[y1 * w + x1]);
+            v += isr_recon_blend(hy, hx, ly, lx, q[y0 * w + x0], q[y0 * w + x1], q[y1 * w + x0], q[y1 * w + x1]);
         }
         out[((size_t)n * cout + c) * hplane + pix] = v;
     }

@@ -40,3 +40,41 @@ __device__ __forceinline__ float isr_pixel_grid(int i, int n)
     return (float)(q - 1.0);
 }
 
+
+// Where VideoTools.warp_upscale(., flow, 4) samples the previous frame for the high-resolution pixel (X, Y), operation by operation as
+// models/videotools.py spells it out (and as assemble_input_kernel does for the unshaded networks): the flow scaled by (-2, +2), resized
+// x4 (align_corners=False), added to the pixel grid; sampler with align_corners=True and zero padding.  b00 = iy0 W + ix0 is the first
+// tap, v* say which of the four taps lie inside the image, w* are their weights; the caller adds ((v00 w00 + v01 w01) + v10 w10) + v11 w11.
+struct IsrWarpTaps {
+    long long b00;
+    int ix0, iy0;
+    bool vx0, vx1, vy0, vy1;
+    float w00, w01, w10, w11;
+};
+
+__device__ __forceinline__ IsrWarpTaps isr_warp_taps(const float* fx, const float* fy, int h, int w, int X, int Y)
+{
+#pragma clang fp contract(off)
+    const int H = 4 * h, W = 4 * w;
+    const float sx_scale = 0.5f * (float)(W - 1), sy_scale = 0.5f * (float)(H - 1);
+    int y0, y1, x0, x1; float ly, lx;
+    isr_src_index_rn(Y, 0.25f, h, y0, y1, ly);
+    isr_src_index_rn(X, 0.25f, w, x0, x1, lx);
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const float flx = isr_bilerp_rn(hy, hx, ly, lx, fx[y0 * w + x0] * -2.0f, fx[y0 * w + x1] * -2.0f, fx[y1 * w + x0] * -2.0f, fx[y1 * w + x1] * -2.0f);
+    const float fly = isr_bilerp_rn(hy, hx, ly, lx, fy[y0 * w + x0] * 2.0f, fy[y0 * w + x1] * 2.0f, fy[y1 * w + x0] * 2.0f, fy[y1 * w + x1] * 2.0f);
+    const float gx = isr_pixel_grid(X, W) + flx;
+    const float gy = isr_pixel_grid(Y, H) + fly;
+    const float gx1 = gx + 1.0f, gy1 = gy + 1.0f;
+    const float sx = gx1 * sx_scale, sy = gy1 * sy_scale;
+    const float fx0 = floorf(sx), fy0 = floorf(sy);
+    IsrWarpTaps t;
+    t.ix0 = (int)fminf(fmaxf(fx0, -2.f), (float)W); t.iy0 = (int)fminf(fmaxf(fy0, -2.f), (float)H);
+    const float wx1 = sx - fx0, wy1 = sy - fy0;
+    const float wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+    t.vx0 = (unsigned)t.ix0 < (unsigned)W; t.vx1 = (unsigned)(t.ix0 + 1) < (unsigned)W;
+    t.vy0 = (unsigned)t.iy0 < (unsigned)H; t.vy1 = (unsigned)(t.iy0 + 1) < (unsigned)H;
+    t.w00 = wx0 * wy0; t.w01 = wx1 * wy0; t.w10 = wx0 * wy1; t.w11 = wx1 * wy1;
+    t.b00 = (long long)t.iy0 * W + t.ix0;
+    return t;
+}

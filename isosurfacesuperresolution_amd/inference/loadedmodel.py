@@ -1,8 +1,11 @@
 """``LoadedModel``: a trained generator plus the per-frame input assembly of the viewer.
 
 Public surface of ``SuperresolutionNetwork/inference/loadedmodel.py`` (attributes ``name, model,
-unshaded, inverse_ao, initial_image_mode, input_channels``; ``inference(current_low, prev_high)``)
-for the unshaded networks of the hot path.  Differences, all additive or forced by the platform:
+unshaded, inverse_ao, initial_image_mode, input_channels`` and, for the colour networks, ``has_normal,
+has_depth, input_single_channels``; ``inference(current_low, prev_high)``) for both families of generators:
+the unshaded networks (mask / normal / depth in, a 6-channel G-buffer out, shaded afterwards) and the shaded
+(colour) networks (RGB + mask and optionally normal and depth in, RGB out; ``loadedmodel.py:36-55,97-118``).
+Differences, all additive or forced by the platform:
 
 * flow hole filling happens on the GPU (``flowfill.fill_flow``) instead of a CPU OpenCV call
   (``loadedmodel.py:77-82``) -- no device round trip inside the frame;
@@ -161,17 +164,54 @@ class LoadedModel:
         r2 = self.upscale_factor ** 2
         self.unshaded = self.input_channels == 5 + 6 * r2 or bool(self.parameters.get('unshaded', False))
         if not self.unshaded:
-            raise NotImplementedError("only the unshaded (mask/normal/depth/ao) networks are on the hot path")
-        self.initial_image_mode = self.parameters.get('initialImage', 'input')
+            # a colour network: RGB + mask, optionally normal and depth, + the flattened previous RGB frame (loadedmodel.py:41-55)
+            self.input_single_channels = self.input_channels - 3 * r2
+            self.has_normal = self.input_single_channels >= 7
+            if self.has_normal:
+                self.input_single_channels -= 3
+            self.has_depth = self.input_single_channels >= 5
+            if self.has_depth:
+                self.input_single_channels -= 1
+        # first frame of a sequence (loadedmodel.py:58-64): colour networks start from zeros, unshaded ones from the upsampled input
+        self.initial_image_mode = self.parameters.get('initialImage', 'input' if self.unshaded else 'zero')
         self.inverse_ao = self.parameters.get('aoInverted', False)
         if str(self.device).startswith("cuda"):
             from .. import ops
             ops.range_reset()             # range guard of the split-operand kernels: a new model starts unflagged
 
+    def select_colour_input(self, current_low):
+        """The colour networks' own channels of the renderer output (loadedmodel.py:98-105); the clamp exists in the first variant only."""
+        if self.has_normal and self.has_depth:
+            return torch.clamp(current_low[:, 0:8], 0, 1)
+        if self.has_normal:
+            return current_low[:, 0:7]
+        if self.has_depth:
+            return torch.cat((current_low[:, 0:4], current_low[:, 7:8]), dim=1)
+        return current_low[:, 0:4]
+
+    def colour_network_input(self, current_low, prev_high):
+        """The colour networks' input [1, c + 48, h, w] of one frame: loadedmodel.py:97-118 up to the network call.
+        ``prev_high`` [1,3,4h,4w]: the previous prediction clamped to [0, 1] (what the caller displays, mainVideo.py:416) or None; then ``initial_image_mode`` selects zeros or the x4 bilinear RGB ("unshaded" has no 3-channel form:
+        ValueError, as in the reference).  The reference warps the initial image as well, so the hole-filled flow is used on the first
+        frame too.  The mask channel is taken as the renderer delivers it, 0 / 1."""
+        r = self.upscale_factor
+        inp = self.select_colour_input(current_low)
+        if prev_high is None:
+            if self.initial_image_mode == "input":
+                prev_high = VideoTools.upscale_bilinear(inp[:, 0:3], r)        # initialImage(.., "input") with its roundings spelled out
+            else:
+                prev_high = initialImage(inp, 3, self.initial_image_mode, self.inverse_ao, r)
+        flow = fill_flow(current_low[:, 8:10], current_low[:, 3:4] != 0)
+        previous_warped = VideoTools.warp_upscale(prev_high.to(self.device), flow, r, special_mask=False)
+        return torch.cat((inp, VideoTools.flatten_high(previous_warped, r)), dim=1)
+
     def inference(self, current_low, prev_high):
         """current_low [1,12,h,w] renderer output (r,g,b,mask,nx,ny,nz,depth,fx,fy,ao,shadow);
-        prev_high [1,6,4h,4w] previous network output or None.  Returns [1,6,4h,4w]."""
+        prev_high [1,6,4h,4w] previous network output or None.  Returns [1,6,4h,4w].
+        Colour networks (``unshaded == False``): prev_high [1,3,4h,4w], returns the RGB prediction [1,3,4h,4w] (unclamped)."""
         with torch.no_grad():
+            if not self.unshaded:
+                return guarded_forward(self.model, self.colour_network_input(current_low, prev_high))
             mask = current_low[:, 3:4]
             inp = torch.cat((mask * 2 - 1, current_low[:, 4:8]), dim=1)
             if prev_high is None:

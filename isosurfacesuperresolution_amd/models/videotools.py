@@ -134,6 +134,19 @@ class VideoTools:
         return out
 
     @staticmethod
+    def upscale_bilinear(image_low, upscale_factor):
+        """Bilinear resize (``align_corners=False``) by an integer factor whose reciprocal is exact, in the explicit form of
+        ``bilinear_taps`` (seven roundings, the resize the warp applies to the flow): what ``utils.initialImage(.., "input")`` obtains
+        from ``F.interpolate`` up to that kernel's roundings, with the operations fixed so that ``isrAssembleInputColour`` computes
+        the same bits.  Other factors take ``F.interpolate``."""
+        r = int(upscale_factor)
+        if (1.0 / r) * r != 1.0:
+            return F.interpolate(image_low, scale_factor=upscale_factor, mode='bilinear', align_corners=False)
+        h, w = image_low.shape[-2:]
+        (y0, y1, ly), (x0, x1, lx), _, _ = VideoTools._warp_plan(h, w, r, image_low.dtype, image_low.device)
+        return bilinear_taps(image_low, y0, y1, ly, x0, x1, lx)
+
+    @staticmethod
     def warp_upscale_library(image_high, flow_low, upscale_factor, special_mask=False):
         """The same warp through ``F.interpolate`` + ``F.grid_sample`` (the reference's calls, videotools.py:51-87): equal to
         ``warp_upscale`` up to the roundings those kernels choose."""

@@ -65,6 +65,14 @@ def _bind(lib):
     lib.isrAssembleInputRows.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]; lib.isrAssembleInputRows.restype = ci
     lib.isrAssembleInputRect.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]; lib.isrAssembleInputRect.restype = ci
     lib.isrAssembleInputPacked.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]; lib.isrAssembleInputPacked.restype = ci
+    if hasattr(lib, "isrAssembleInputColour"):        # (an older build loaded through ISR_SR_LIB for an A/B run has no colour entry points)
+        lib.isrAssembleInputColour.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]; lib.isrAssembleInputColour.restype = ci
+        lib.isrFinishFrameColour.argtypes = [vp, vp, vp, ci, ci, vp]; lib.isrFinishFrameColour.restype = ci
+        lib.isrConvSmallFinishFrameColour.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ll, vp]; lib.isrConvSmallFinishFrameColour.restype = ci
+        lib.isrConvTailWorkspaceBytes3.argtypes = [ci, ci]; lib.isrConvTailWorkspaceBytes3.restype = ll
+        lib.isrConvTailPrepare3.argtypes = [vp, vp, vp]; lib.isrConvTailPrepare3.restype = ci
+        lib.isrConvTailFinishFrame3.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ll, vp]; lib.isrConvTailFinishFrame3.restype = ci
+        lib.isrConvTailFinishFrame3Packed.argtypes = lib.isrConvTailFinishFrame3.argtypes; lib.isrConvTailFinishFrame3Packed.restype = ci
     lib.isrConvSmallCinPad.argtypes = [ci]; lib.isrConvSmallCinPad.restype = ci
     lib.isrConvSmallWeightFloats.argtypes = [ci]; lib.isrConvSmallWeightFloats.restype = ll
     lib.isrConvSmallPrepare.argtypes = [vp, vp, vp, vp, ci, ci, vp]; lib.isrConvSmallPrepare.restype = ci
@@ -299,7 +307,10 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  # the frame's small kernels (zero algorithmic flops; registered for bench.py's gap accounting)
                  25: "trunk_pack_input_kernel", 26: "assemble_input_kernel", 27: "tail_finish_kernel", 28: "flow_fill_one_kernel",
                  29: "finish_frame_kernel", 30: "ups_frame_kernel", 31: "conv3x3_split_upsp_kernel",
-                 32: "conv3x3_wgrad_split_kernel"}
+                 32: "conv3x3_wgrad_split_kernel",
+                 # the colour networks' frame kernels (33 carries the tail's matrix work; 34-36 are small kernels)
+                 33: "conv3x3_split_tail_colour_kernel", 34: "tail_finish_colour_kernel", 35: "assemble_input_colour_kernel",
+                 36: "finish_frame_colour_kernel"}
 
 
 def debug_switches():
@@ -1800,7 +1811,8 @@ _tail_ws = {}
 
 
 def _prepare_tail(weight8):
-    """The last layer's weights [6, 64, 3, 3] by (tap, channel) row in the z stage's operand order, cached like ``prepare_weights``."""
+    """The last layer's weights [6, 64, 3, 3] (colour networks: [3, 64, 3, 3]) by (tap, channel) row in the z stage's operand order,
+    cached like ``prepare_weights``."""
     lib = _sr()
     key = id(weight8)
     hit = _tail_cache.get(key)
@@ -1809,7 +1821,8 @@ def _prepare_tail(weight8):
         if ref() is weight8 and version == weight8._version and ptr == weight8.data_ptr() and epoch == _images_epoch:
             return wz
     wz = torch.empty(lib.isrConvTailWeightBytes(), dtype=torch.uint8, device=weight8.device)
-    rc = lib.isrConvTailPrepare(_ptr(weight8.detach().contiguous()), _ptr(wz), _stream())
+    prepare = lib.isrConvTailPrepare3 if weight8.shape[0] == 3 else lib.isrConvTailPrepare
+    rc = prepare(_ptr(weight8.detach().contiguous()), _ptr(wz), _stream())
     if rc != 0:
         raise RuntimeError("isrConvTailPrepare failed (%d)" % rc)
     if len(_tail_cache) > 64:
@@ -2067,3 +2080,123 @@ def finish_frame(raw, net_input, shading=None):
     if rc != 0:
         raise RuntimeError("isrFinishFrame failed (%d)" % rc)
     return nxt, rgb
+
+
+# ---- colour networks (RGB in, RGB out; inference.LoadedModel with ``unshaded == False``) -------------------------------------------
+# The two ends of the frame that depend on what the network is for: the input assembly (channel selection + warp and space-to-depth of
+# the previous RGB frame) and the finishing (residual reconstruction over [0, 1, 2] + clamp), standalone, behind the small-Cout last
+# layer, and behind the fused tail with three output channels.  One [1, 3, 4h, 4w] tensor is the displayed RGB and the next ``prev_high``.
+COLOUR_VARIANTS = (8, 7, 5, 4)          # number of selected G-buffer channels: normal + depth, normal, depth, neither
+
+
+def assemble_input_colour(gbuffer_hwc, flow_filled, prev_high, variant, initial_image="zero", out=None):
+    """Renderer G-buffer [h,w,12] (+ hole-filled flow [1,2,h,w], previous frame [1,3,4h,4w] or None) -> the colour network's input
+    [1, variant + 48, h, w] in one launch (``isrAssembleInputColour``).  ``variant``: 8 | 7 | 5 | 4 selected channels
+    (``LoadedModel.input_single_channels`` + 3 for normal + 1 for depth).  Without a previous frame ``initial_image`` "zero" needs no
+    flow; "input" (the x4 bilinear RGB, warped like any previous frame) does; "unshaded" raises ValueError as ``utils.initialImage``."""
+    assert gbuffer_hwc.is_cuda and gbuffer_hwc.is_contiguous() and gbuffer_hwc.shape[-1] == 12
+    if variant not in COLOUR_VARIANTS:
+        raise ValueError("assemble_input_colour: variant must be one of %s" % (COLOUR_VARIANTS,))
+    if prev_high is None and initial_image == "unshaded":
+        raise ValueError("for mode='unshaded', channels is expected to be 5 or 6")
+    h, w = gbuffer_hwc.shape[0], gbuffer_hwc.shape[1]
+    if out is None:
+        out = torch.empty((1, variant + 48, h, w), dtype=torch.float32, device=gbuffer_hwc.device)
+    assert tuple(out.shape) == (1, variant + 48, h, w) and out.is_contiguous()
+    need_flow = prev_high is not None or initial_image == "input"
+    if need_flow:
+        if flow_filled is None:
+            raise ValueError("assemble_input_colour: the hole-filled flow is needed (a previous frame, or initial image 'input')")
+        flow_filled = flow_filled.contiguous()
+        assert flow_filled.shape == (1, 2, h, w)
+    if prev_high is not None:
+        prev_high = prev_high.contiguous()
+        assert prev_high.shape == (1, 3, 4 * h, 4 * w)
+    rc = _sr().isrAssembleInputColour(_ptr(gbuffer_hwc), _ptr(flow_filled) if need_flow else None, _ptr(prev_high), _ptr(out), h, w,
+                                      int(variant), INIT_MODES[initial_image] if prev_high is None else 0, _stream())
+    if rc != 0:
+        raise RuntimeError("isrAssembleInputColour failed (%d)" % rc)
+    return out
+
+
+def finish_frame_colour(raw, net_input):
+    """Conv output before reconstruction [1,3,4h,4w] + network input [1,>=3,h,w] -> clamp(raw + bilinear x4 of net_input[:, :3], 0, 1)
+    in one launch (``isrFinishFrameColour``): ``clamp(ops.recon_residual(raw, net_input, 3), 0, 1)`` bit for bit."""
+    raw = raw.contiguous()
+    net_input = net_input.contiguous()
+    assert raw.is_cuda and raw.shape[0] == 1 and raw.shape[1] == 3 and net_input.shape[1] >= 3
+    _, _, H, W = raw.shape
+    out = torch.empty_like(raw)
+    rc = _sr().isrFinishFrameColour(_ptr(raw), _ptr(net_input), _ptr(out), H // 4, W // 4, _stream())
+    if rc != 0:
+        raise RuntimeError("isrFinishFrameColour failed (%d)" % rc)
+    return out
+
+
+def final_conv_finish_colour(features, weight, bias, net_input):
+    """The colour network's last layer (64 -> 3, the exact small-Cout kernel) and ``finish_frame_colour`` in one launch
+    (``isrConvSmallFinishFrameColour``) -- the route of frames whose layers the range guard has sent to the exact kernels."""
+    assert features.is_cuda and features.shape[0] == 1 and weight.shape[0] == 3
+    w8, b8 = _prepare_small(weight, bias)
+    features, xp, _ = _plane_strides(features)
+    net_input = net_input.contiguous()
+    _, cin, H, W = features.shape
+    out = torch.empty((1, 3, H, W), dtype=torch.float32, device=features.device)
+    rc = _sr().isrConvSmallFinishFrameColour(_ptr(features), _ptr(w8), _ptr(b8), _ptr(net_input), _ptr(out), cin, H // 4, W // 4, xp, _stream())
+    if rc != 0:
+        raise RuntimeError("isrConvSmallFinishFrameColour failed (%d)" % rc)
+    return out
+
+
+def tail_supported_colour(features, weight6, weight8):
+    """``tail_supported`` for a colour network: 64 -> 64 -> 3 channels."""
+    if not (TAIL_FUSION and SPLIT_F16 and not FAST_F16 and features.is_cuda and features.dtype == torch.float32):
+        return False
+    if any_hot(features.device):          # range guard: a layer of this model needs the exact kernels -- per-layer routing only
+        return False
+    if features.dim() != 4 or features.shape[0] != 1 or features.shape[1] != 64 or features.shape[2] % 4 or features.shape[3] % 4:
+        return False
+    if tuple(weight6.shape) != (64, 64, 3, 3) or tuple(weight8.shape) != (3, 64, 3, 3):
+        return False
+    f, xp, _ = _plane_strides(features)
+    return f is features and bool(_sr().isrConvTailSupported(_ptr(features), features.shape[2] // 4, features.shape[3] // 4, xp))
+
+
+_tail_ws_colour = {}
+
+
+def tail_conv_finish_colour(features, weight6, bias6, weight8, bias8, net_input, out=None):
+    """``tail_conv_finish`` for a colour network: features [1,64,4h,4w] (fp32, or a ``PackedSplit``) -> relu(conv3x3(., weight6) +
+    bias6) -> conv3x3(., weight8 [3,64,3,3]) + bias8 -> ``finish_frame_colour``, in two launches (``isrConvTailFinishFrame3``): nine
+    S planes and 27 rows of the extra product instead of eighteen and 54.  Returns [1,3,4h,4w] (``out`` to write into)."""
+    lib = _sr()
+    packed = isinstance(features, PackedSplit)
+    if packed:
+        H, W, xp, dev = features.h, features.w, features.plane, features.data.device
+        assert features.channels == 64
+    else:
+        features, xp, _ = _plane_strides(features)
+        _, _, H, W = features.shape
+        dev = features.device
+    assert tuple(weight8.shape) == (3, 64, 3, 3) and net_input.shape[1] >= 3
+    net_input = net_input.contiguous()
+    h, w = H // 4, W // 4
+    wq6 = _prepare_split(weight6)
+    wz = _prepare_tail(weight8)
+    key = (dev, h, w, torch.cuda.current_stream().cuda_stream)
+    ws = _tail_ws_colour.get(key)
+    if ws is None:
+        ws = torch.empty(lib.isrConvTailWorkspaceBytes3(h, w), dtype=torch.uint8, device=dev)
+        _tail_ws_colour[key] = ws
+    if out is None:
+        out = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+    assert tuple(out.shape) == (1, 3, H, W) and out.is_contiguous() and out.dtype == torch.float32
+    b6 = bias6.detach().contiguous() if bias6 is not None else None
+    b8 = bias8.detach().contiguous() if bias8 is not None else torch.zeros(3, dtype=torch.float32, device=dev)
+    _arm_range(("tail", id(weight6)), dev, members=[id(weight6)])         # the largest |y6|: the intermediate is split in registers inside the kernel
+    fn = lib.isrConvTailFinishFrame3Packed if packed else lib.isrConvTailFinishFrame3
+    rc = fn(_ptr(features.data if packed else features), _ptr(wq6), _ptr(b6), _ptr(wz), _ptr(b8), _ptr(ws), _ptr(net_input), _ptr(out),
+            h, w, xp, _stream())
+    if rc != 0:
+        raise RuntimeError("isrConvTailFinishFrame3 failed (%d)" % rc)
+    return out

@@ -78,6 +78,9 @@ class StripSuperResolution:
     def __init__(self, model, shading, process_group=None, halo=HALO, grid=None):
         """model: inference.LoadedModel; shading: utils.ScreenSpaceShading.  ``grid``: None = horizontal strips (world x 1),
         (rows, columns) with rows * columns == world size, or "auto" (``best_grid`` of the first frame's size)."""
+        if not getattr(model, 'unshaded', True):
+            raise NotImplementedError("StripSuperResolution splits frames of the unshaded networks only; a colour (RGB) model runs "
+                                      "whole frames through pipeline.SuperResolutionPipeline")
         self.grid = grid
         self.model = model
         self.shading = shading

@@ -33,6 +33,41 @@ def default_shading(device, fov=30.0):
     return sh
 
 
+def run_network_colour(model, x, after_trunk=None, prefetch_point="trunk"):
+    """``run_network`` for a colour model: input [1,c+48,h,w] -> the frame [1,3,4h,4w], clamp(prediction, 0, 1) -- the displayed RGB
+    and the next frame's ``prev_high`` in one tensor.  The same routing: dataflow trunk -> postblock.1 -> postblock.4 (packed-split
+    where ``ops.packed_supported``) -> the three-channel fused tail (``ops.tail_conv_finish_colour``); with a layer on the range
+    guard's exact route, the per-layer kernels and the small-Cout last layer with the colour finishing in its epilogue."""
+    net = model.model
+    last, six, four = net.postblock[8], net.postblock[6], net.postblock[4]
+    tail = ops.TAIL_FUSION and ops.SPLIT_F16 and not ops.FAST_F16 and not ops.any_hot(x.device) \
+        and tuple(six.weight.shape) == (64, 64, 3, 3) and tuple(last.weight.shape) == (3, 64, 3, 3)
+    f4 = None
+    if tail:
+        f2 = net.forward_features(x, last_three=False, after_trunk=after_trunk if prefetch_point == "trunk" else None)
+        if prefetch_point in ("trunk", "ups1"):
+            if prefetch_point == "ups1" and after_trunk is not None:
+                after_trunk()
+            after_trunk = None
+        if ops.packed_supported(f2, four.weight, True):
+            f4 = ops.conv3x3_split_packed(f2, four.weight, four.bias, act='relu', upsample2x=True)
+        else:
+            f4 = ops.conv3x3(f2, four.weight, four.bias, act='relu', upsample2x=True)
+        if after_trunk is not None and prefetch_point != "tail":
+            after_trunk(); after_trunk = None                # "ups2": beside the fused tail
+    if isinstance(f4, ops.PackedSplit) or (f4 is not None and ops.tail_supported_colour(f4, six.weight, last.weight)):
+        frame = ops.tail_conv_finish_colour(f4, six.weight, six.bias, last.weight, last.bias, x)
+    elif f4 is not None:
+        f6 = ops.conv3x3(f4, six.weight, six.bias, act='relu')
+        frame = ops.final_conv_finish_colour(f6, last.weight, last.bias, x)
+    else:
+        frame = ops.final_conv_finish_colour(net.forward_features(x, last_layer=False, after_trunk=after_trunk), last.weight, last.bias, x)
+        after_trunk = None
+    if after_trunk is not None:
+        after_trunk()
+    return frame
+
+
 def run_network(model, shading, x, after_trunk=None, prefetch_point="trunk", out=None):
     """The network and the frame's finishing on the fused HIP path: input [1,101,h,w] -> (raw [1,6,4h,4w] clamped / normalised,
     rgb [1,3,4h,4w]).  ``model``: inference.LoadedModel; ``after_trunk``: callable run once at ``prefetch_point`` (the frame
@@ -95,18 +130,34 @@ def run_network(model, shading, x, after_trunk=None, prefetch_point="trunk", out
     return raw, rgb
 
 
+def is_colour(model):
+    """A colour model (RGB in, RGB out): ``inference.LoadedModel`` says so."""
+    return not getattr(model, 'unshaded', True)
+
+
 def fused_path_ok(model, upscale=4):
-    """The fused frame kernels take this network: 4x, residual reconstruction over the five input channels."""
+    """The fused frame kernels take this network: 4x, residual reconstruction over the five input channels -- or, a colour model, over
+    [0, 1, 2] with three outputs, bilinear upsampling and no batch norm."""
     net = model.model
-    return upscale == 4 and getattr(net, 'recon_type', None) == 'residual' \
-        and getattr(net, 'channel_mask', None) is not None and len(net.channel_mask) == 5
+    if upscale != 4 or getattr(net, 'recon_type', None) != 'residual' or getattr(net, 'channel_mask', None) is None:
+        return False
+    if is_colour(model):
+        return list(net.channel_mask) == [0, 1, 2] and getattr(net, 'output_channels', None) == 3 \
+            and getattr(net, 'upsample', None) == 'bilinear' and not getattr(net, 'use_bn', True) and hasattr(net, 'forward_features') \
+            and model.input_channels - 48 in ops.COLOUR_VARIANTS
+    return len(net.channel_mask) == 5
 
 
 class SuperResolutionPipeline:
     def __init__(self, renderer, model, shading, low_res, upscale=4, temporal=True, device="cuda", fused=True, graph=None):
         """``graph`` (default: ISR_FRAME_GRAPH=1): steady-state frames -- temporal sequence, next frame's camera known -- replay as
         ONE HIP graph per frame (``_frame_graph``).  The returned tensors are then the pipeline's static output buffers: valid
-        until the frame after next overwrites them."""
+        until the frame after next overwrites them.  NOT for colour models: the graph's static buffers are the unshaded networks'
+        six-channel ones, so with a colour model ``graph`` is switched off and every frame runs eagerly.
+
+        Colour models (``model.unshaded == False``; RGB in, RGB out): ``frame`` returns ``(rgb, raw)`` with BOTH [1,3,4h,4w] and the
+        same values -- the prediction clamped to [0, 1], which is the displayed image and ``self.previous`` (mainVideo.py:416);
+        ``shading`` is not used."""
         self.renderer = renderer
         self.model = model            # inference.LoadedModel
         self.shading = shading
@@ -157,10 +208,11 @@ class SuperResolutionPipeline:
         self.foreground_variant = 0       # kernel variant of frames rendered on the main stream
         # fused=True: input assembly and frame finishing run as two HIP kernels (ops.assemble_input /
         # ops.finish_frame); fused=False: the module-level PyTorch path (LoadedModel.inference etc.)
+        self.colour = is_colour(model)
         self.fused = fused and fused_path_ok(model, upscale)
         # ---- the frame as one HIP graph ------------------------------------------------------------------------
         self.graph = (os.environ.get("ISR_FRAME_GRAPH", "0") == "1") if graph is None else bool(graph)
-        self.graph = self.graph and self.fused and self._render_stream is not None
+        self.graph = self.graph and self.fused and self._render_stream is not None and not self.colour
         self._graphs = [None, None]       # per G-buffer slot: the frame whose G-buffer sits in slot s (and renders the next one into s ^ 1)
         self._graph_sig = None
         self._graph_pool = None
@@ -268,6 +320,10 @@ class SuperResolutionPipeline:
 
     def superresolve(self, low):
         raw = self.model.inference(low, self.previous if self.temporal else None)
+        if self.colour:
+            # mainVideo.py:416, mainPSNR4_ColoredNets.py:167: the clamped prediction is displayed and fed back
+            self.previous = torch.clamp(raw, 0, 1)
+            return self.previous
         # mainGUI.py:594-599 -- this tensor is also next frame's "previous high-res" input
         raw = torch.cat([torch.clamp(raw[:, 0:1], -1, +1),
                          ScreenSpaceShading.normalize(raw[:, 1:4], dim=1),
@@ -279,6 +335,8 @@ class SuperResolutionPipeline:
         """The network input of a frame: packed-split straight into the dataflow trunk's workspace where that launch will take it
         (ops.assemble_input_packed), fp32 planes otherwise."""
         net = self.model.model
+        if self.colour:
+            return ops.assemble_input_colour(gbuffer, flow, prev, self.model.input_channels - 48, self.model.initial_image_mode)
         if self.fused and hasattr(net, 'trunk_convs'):
             x = ops.assemble_input_packed(gbuffer, flow, prev, net.trunk_convs(), self.model.initial_image_mode, self.model.inverse_ao)
             if x is not None:
@@ -286,7 +344,10 @@ class SuperResolutionPipeline:
         return ops.assemble_input(gbuffer, flow, prev, self.model.initial_image_mode, self.model.inverse_ao)
 
     def _network(self, x, after_trunk=None, out=None):
-        """Network input [1,101,h,w] -> (raw [1,6,4h,4w] clamped / normalised, rgb [1,3,4h,4w])."""
+        """Network input [1,101,h,w] -> (raw [1,6,4h,4w] clamped / normalised, rgb [1,3,4h,4w]); colour models: both the frame [1,3,4h,4w]."""
+        if self.colour:
+            frame = run_network_colour(self.model, x, after_trunk=after_trunk, prefetch_point=self.prefetch_point)
+            return frame, frame
         return run_network(self.model, self.shading, x, after_trunk=after_trunk, prefetch_point=self.prefetch_point, out=out)
 
     # ---- one HIP graph per frame ---------------------------------------------------------------------------------------------
@@ -402,7 +463,7 @@ class SuperResolutionPipeline:
                 self.renderer.gate_resident(torch.cuda.current_stream())
             prev = self.previous if self.temporal else None
             flow = None
-            if prev is not None:
+            if prev is not None or (self.colour and self.model.initial_image_mode == "input"):   # (a colour model's initial image is warped too)
                 flow = self._flows[self._slot] if self._flow_ready[self._slot] else ops.fill_flow_gbuffer(g)
             x = self._assemble(g, flow, prev)
             self._consumed[self._slot].record(torch.cuda.current_stream())   # G-buffer no longer needed
@@ -433,6 +494,8 @@ class SuperResolutionPipeline:
         with torch.no_grad():
             low = self.render_low(origin)
             raw = self.superresolve(low)
+            if self.colour:
+                return raw, raw
             self.shading.inverse_ao = self.model.inverse_ao
             rgb = self.shading(raw)
         return rgb, raw

@@ -204,6 +204,10 @@ def load_models(specs, device, upscaling=UPSCALING):
             net = LoadedModel(m["path"], device, upscaling).model
         else:
             net = SimpleUpsample(upscaling, m["name"]).to(device)
+        if not isinstance(net, SimpleUpsample) and getattr(net, "output_channels", 6) != 6:
+            # the clips, the recurrence of run_clip and every column are those of the 6-channel unshaded networks (mainPSNR3_AllStats.py)
+            raise NotImplementedError("stats: model '%s' has %d output channels; only the unshaded (mask / normal / depth / AO) networks "
+                                      "are evaluated here, not the colour (RGB) ones" % (m["name"], net.output_channels))
         out.append((m["name"], net))
     return out
 
