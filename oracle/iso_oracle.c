@@ -24,7 +24,8 @@
 
 /* ------------------------------------------------------------------ volume */
 
-iso_volume* iso_volume_create(const float* dense, int nx, int ny, int nz)
+/* degenerate_ok: a tile takes its world map from the global volume, so its own extent may be zero */
+static iso_volume* volume_create(const float* dense, int nx, int ny, int nz, int degenerate_ok)
 {
     if (!dense || nx <= 0 || ny <= 0 || nz <= 0 || nx > 4096 || ny > 4096 || nz > 4096) return NULL;
     iso_volume* v = (iso_volume*)calloc(1, sizeof(iso_volume));
@@ -96,12 +97,23 @@ iso_volume* iso_volume_create(const float* dense, int nx, int ny, int nz)
     double m = ext[0];
     if (ext[1] > m) m = ext[1];
     if (ext[2] > m) m = ext[2];
+    /* A single active voxel has no extent: the reference's 1 / max(extent) is infinite there.  Refused like an empty grid,
+     * as the product does (finalizeVolume; DESIGN.md, deviations). */
+    if (!(m > 0) && !degenerate_ok) {
+        iso_volume_free(v);
+        return NULL;
+    }
     double scale = 1.0 / m;
     /* postTranslate(-centre) then postScale(scale) on a unit UniformScaleMap */
     v->s = 1.0 * scale;
     v->sinv = 1.0 / v->s;
     for (int k = 0; k < 3; ++k) v->t[k] = (-cen[k]) * scale;
     return v;
+}
+
+iso_volume* iso_volume_create(const float* dense, int nx, int ny, int nz)
+{
+    return volume_create(dense, nx, ny, nz, 0);
 }
 
 /* Tile of a larger volume (tests of the multi-GPU tiled render): same rules as the product's
@@ -123,12 +135,12 @@ iso_volume* iso_volume_create_tile(const float* dense, int nx, int ny, int nz, c
     int any = 0;
     for (size_t i = 0; i < n && !any; ++i) any = dense[i] != 0.0f;
     iso_volume* v;
-    if (any) v = iso_volume_create(dense, nx, ny, nz);
+    if (any) v = volume_create(dense, nx, ny, nz, 1);
     else {
         float* tmp = (float*)malloc(n * sizeof(float));
         memcpy(tmp, dense, n * sizeof(float));
         tmp[0] = 1.0f;                       /* build the containers, then forget the dummy voxel */
-        v = iso_volume_create(tmp, nx, ny, nz);
+        v = volume_create(tmp, nx, ny, nz, 1);
         free(tmp);
         if (v) { v->data[0] = 0.0f; memset(v->leaf, 0, (size_t)v->bx * v->by * v->bz); }
     }
@@ -159,6 +171,7 @@ iso_volume* iso_volume_create_tile(const float* dense, int nx, int ny, int nz, c
     double m = ext[0];
     if (ext[1] > m) m = ext[1];
     if (ext[2] > m) m = ext[2];
+    if (!(m > 0)) { iso_volume_free(v); return NULL; }
     double scale = 1.0 / m;
     v->s = 1.0 * scale;
     v->sinv = 1.0 / v->s;

@@ -75,7 +75,7 @@ class OracleVolume:
         else:
             self._h = lib().iso_volume_create(dense.ctypes.data, nx, ny, nz)
         if not self._h:
-            raise ValueError("oracle: empty or oversized volume")
+            raise ValueError("oracle: empty, oversized or zero-extent (a single active voxel) volume")
         self.shape = dense.shape
 
     def info(self):
