@@ -217,7 +217,6 @@ def _ptr(t):
 # captured optimizer kernels on the parameters' memory without touching the Python-side version counter.  Whoever changes
 # weights behind autograd's back therefore calls ``invalidate_weight_images()``; every cached image carries the epoch
 # it was made in and is rebuilt when the epoch has moved on.
-_wcache = {}
 _images_epoch = 0
 
 
@@ -225,6 +224,38 @@ def invalidate_weight_images():
     """Declare every cached kernel-layout weight image (exact, small-Cout, fp16 / bf16, split) stale."""
     global _images_epoch
     _images_epoch += 1
+
+
+class _WeightImages:
+    """The kernel-layout images of one kernel family: ``key`` (the caller's: id(weight) and the layout flags) -> image, valid while
+    the rule above holds for ``tensors`` -- (weight,), or (weight, bias-or-None) where the image holds the bias too."""
+
+    def __init__(self, cap=512):
+        self.cap, self.entries = cap, {}
+
+    @staticmethod
+    def _stamp(tensors):
+        return tuple((t._version, t.data_ptr()) if t is not None else None for t in tensors)
+
+    def lookup(self, key, tensors):
+        hit = self.entries.get(key)
+        if hit is not None and hit[0]() is tensors[0] and hit[1] == self._stamp(tensors) and hit[3] == _images_epoch:
+            return hit[2]
+        return None
+
+    def store(self, key, tensors, image):
+        # Beyond the cap only entries whose weight is dead go, never a live one: a captured frame (pipeline._frame_graph) or a
+        # launch in flight may hold the image's address.
+        if len(self.entries) > self.cap:
+            for k in [k for k, v in self.entries.items() if v[0]() is None]:
+                del self.entries[k]
+        self.entries[key] = (weakref.ref(tensors[0]), self._stamp(tensors), image, _images_epoch)
+
+    def clear(self):
+        self.entries.clear()
+
+
+_wcache = _WeightImages()
 
 
 # ---- routing epoch: what a CAPTURED frame (pipeline.SuperResolutionPipeline, ISR_FRAME_GRAPH) has baked in ----------------------
@@ -272,11 +303,9 @@ def prepare_weights(weight, transpose_flip=False):
     lib = _sr()
     cout, cin = weight.shape[0], weight.shape[1]
     key = (id(weight), bool(transpose_flip))
-    hit = _wcache.get(key)
-    if hit is not None:
-        ref, version, ptr, wp, epoch = hit
-        if ref() is weight and version == weight._version and ptr == weight.data_ptr() and epoch == _images_epoch:
-            return wp
+    wp = _wcache.lookup(key, (weight,))
+    if wp is not None:
+        return wp
     w = weight.detach().contiguous()
     if transpose_flip:
         cin_pad, cout_pad = lib.isrConvCinPad(cout), lib.isrConvCoutPad(cin)
@@ -286,10 +315,7 @@ def prepare_weights(weight, transpose_flip=False):
     rc = lib.isrConvPrepareWeights(_ptr(w), _ptr(wp), cout, cin, 1 if transpose_flip else 0, _stream())
     if rc != 0:
         raise RuntimeError("isrConvPrepareWeights failed (%d)" % rc)
-    if len(_wcache) > 512:
-        for k in [k for k, v in _wcache.items() if v[0]() is None]:
-            del _wcache[k]
-    _wcache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wp, _images_epoch)
+    _wcache.store(key, (weight,), wp)
     return wp
 
 
@@ -352,20 +378,15 @@ def profile_records():
     return out
 
 
-_small_cache = {}
+_small_cache = _WeightImages(64)
 
 
 def _prepare_small(weight, bias):
     """(w8, bias8) device tensors for the Cout <= 8 kernel, cached like prepare_weights."""
     lib = _sr()
-    key = id(weight)
-    hit = _small_cache.get(key)
-    bptr = bias.data_ptr() if bias is not None else 0
-    bver = bias._version if bias is not None else 0
+    hit = _small_cache.lookup(id(weight), (weight, bias))
     if hit is not None:
-        ref, ver, ptr, bp, bv, w8, b8, epoch = hit
-        if ref() is weight and ver == weight._version and ptr == weight.data_ptr() and bp == bptr and bv == bver and epoch == _images_epoch:
-            return w8, b8
+        return hit
     cout, cin = weight.shape[0], weight.shape[1]
     w8 = torch.empty(lib.isrConvSmallWeightFloats(cin), dtype=torch.float32, device=weight.device)
     b8 = torch.empty(8, dtype=torch.float32, device=weight.device)
@@ -373,9 +394,7 @@ def _prepare_small(weight, bias):
                                  _ptr(w8), _ptr(b8), cout, cin, _stream())
     if rc != 0:
         raise RuntimeError("isrConvSmallPrepare failed (%d)" % rc)
-    if len(_small_cache) > 64:
-        _small_cache.clear()
-    _small_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), bptr, bver, w8, b8, _images_epoch)
+    _small_cache.store(id(weight), (weight, bias), (w8, b8))
     return w8, b8
 
 
@@ -449,7 +468,7 @@ def _launch_forward(x, wprep, bias, residual, cin, cout, act, slope, upsample2x,
 # ``isrConv3x3ForwardF16`` (operands rounded to fp16, fp32 accumulation, fp32 tensors).  Off by default: the 1e-4
 # parity with the reference's CPU path is a property of the fp32 kernels.  bench.py reports it separately with its PSNR.
 FAST_F16 = False
-_f16_cache = {}
+_f16_cache = _WeightImages()
 
 
 def _prepare_lp(weight, transpose_flip=False, bf16=False):
@@ -457,11 +476,9 @@ def _prepare_lp(weight, transpose_flip=False, bf16=False):
     data-gradient weights w'[ci][co][ky][kx] = w[co][ci][2-ky][2-kx]."""
     lib = _sr()
     key = (id(weight), bool(transpose_flip), bool(bf16))
-    hit = _f16_cache.get(key)
-    if hit is not None:
-        ref, version, ptr, wq, epoch = hit
-        if ref() is weight and version == weight._version and ptr == weight.data_ptr() and epoch == _images_epoch:
-            return wq
+    wq = _f16_cache.lookup(key, (weight,))
+    if wq is not None:
+        return wq
     w = weight.detach()
     if transpose_flip:
         w = w.flip(2, 3).transpose(0, 1)
@@ -471,20 +488,13 @@ def _prepare_lp(weight, transpose_flip=False, bf16=False):
     rc = (lib.isrConvBf16Prepare if bf16 else lib.isrConvF16Prepare)(_ptr(w), _ptr(wq), cout, cin, _stream())
     if rc != 0:
         raise RuntimeError("isrConv%sPrepare failed (%d)" % ("Bf16" if bf16 else "F16", rc))
-    if len(_f16_cache) > 512:
-        for k in [k for k, v in _f16_cache.items() if v[0]() is None]:
-            del _f16_cache[k]
-    _f16_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wq, _images_epoch)
+    _f16_cache.store(key, (weight,), wq)
     return wq
 
 
-def _prepare_f16(weight):
-    return _prepare_lp(weight)
-
-
-def _launch_lp(x, wq, bias, residual, cout, act, slope, upsample2x, bf16, packed=False):
-    """One launch of isrConv3x3ForwardF16 / Bf16 (x: fp32 NCHW, channel planes may be padded; ``packed`` as in
-    ``_launch_forward``)."""
+def _launch_lp(symbol, x, wq, bias, residual, cout, act, slope, upsample2x, packed=False):
+    """One launch of the library's ``symbol`` = "isrConv3x3ForwardF16" / "...Bf16" / "...Split", which share one signature (x: fp32
+    NCHW, channel planes may be padded; ``packed`` as in ``_launch_forward``)."""
     lib = _sr()
     x, xp, xi = _plane_strides(x)
     fuse = False
@@ -498,11 +508,10 @@ def _launch_lp(x, wq, bias, residual, cout, act, slope, upsample2x, bf16, packed
     if residual is not None:
         residual, rp, ri = _plane_strides(residual)
     y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device) if packed else empty_planes(n, cout, h, w, x.device)
-    fn = lib.isrConv3x3ForwardBf16 if bf16 else lib.isrConv3x3ForwardF16
-    rc = fn(_ptr(x), _ptr(wq), _ptr(bias), _ptr(residual), _ptr(y), n, cin, h, w, cout, ACT_CODES[act], float(slope),
-            1 if fuse else 0, xp, xi, y.stride(1), cout * y.stride(1), rp, ri, _stream())
+    rc = getattr(lib, symbol)(_ptr(x), _ptr(wq), _ptr(bias), _ptr(residual), _ptr(y), n, cin, h, w, cout, ACT_CODES[act], float(slope),
+                              1 if fuse else 0, xp, xi, y.stride(1), cout * y.stride(1), rp, ri, _stream())
     if rc != 0:
-        raise RuntimeError("isrConv3x3Forward%s failed (%d)" % ("Bf16" if bf16 else "F16", rc))
+        raise RuntimeError("%s failed (%d)" % (symbol, rc))
     return y
 
 
@@ -511,8 +520,8 @@ def conv3x3_f16(x, weight, bias=None, act='none', slope=0.01, residual=None, ups
     if act not in ('none', 'relu', 'leaky'):
         raise ValueError("unknown activation %r" % (act,))
     with torch.no_grad():
-        return _launch_lp(x, _prepare_lp(weight), bias.contiguous() if bias is not None else None, residual, weight.shape[0],
-                          act, slope, upsample2x, False)
+        return _launch_lp("isrConv3x3ForwardF16", x, _prepare_lp(weight), bias.contiguous() if bias is not None else None, residual,
+                          weight.shape[0], act, slope, upsample2x)
 
 
 # ---- range guard of the split-operand path, and the per-frame guard words ---------------------------------------------------
@@ -714,7 +723,7 @@ def range_check_due(device):
 # against fp64 that matches the exact fp32 kernel's (tests/test_conv_gpu.py).  SPLIT_F16 = False restores the exact
 # k-ordered fmaf-chain kernels of sr_conv3x3.hip (training always uses those).
 SPLIT_F16 = True
-_split_cache = {}
+_split_cache = _WeightImages()
 
 
 def _prepare_split(weight, transpose_flip=False):
@@ -722,11 +731,9 @@ def _prepare_split(weight, transpose_flip=False):
     transpose_flip: the data-gradient weights w'[ci][co][ky][kx] = w[co][ci][2-ky][2-kx]."""
     lib = _sr()
     key = (id(weight), bool(transpose_flip))
-    hit = _split_cache.get(key)
-    if hit is not None:
-        ref, version, ptr, wq, epoch = hit
-        if ref() is weight and version == weight._version and ptr == weight.data_ptr() and epoch == _images_epoch:
-            return wq
+    wq = _split_cache.lookup(key, (weight,))
+    if wq is not None:
+        return wq
     w = weight.detach()
     if transpose_flip:
         w = w.flip(2, 3).transpose(0, 1)
@@ -736,16 +743,12 @@ def _prepare_split(weight, transpose_flip=False):
     rc = lib.isrConvSplitPrepare(_ptr(w), _ptr(wq), cout, cin, _stream())
     if rc != 0:
         raise RuntimeError("isrConvSplitPrepare failed (%d)" % rc)
-    if len(_split_cache) > 512:
-        for k in [k for k, v in _split_cache.items() if v[0]() is None]:
-            del _split_cache[k]
-    _split_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wq, _images_epoch)
+    _split_cache.store(key, (weight,), wq)
     return wq
 
 
 def _split_cached(weight, transpose_flip):
-    hit = _split_cache.get((id(weight), bool(transpose_flip)))
-    return hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr() and hit[4] == _images_epoch
+    return _split_cache.lookup((id(weight), bool(transpose_flip)), (weight,)) is not None
 
 
 def prepare_split_many(weights):
@@ -770,8 +773,8 @@ def prepare_split_many(weights):
         if rc != 0:
             raise RuntimeError("isrConvSplitPrepareMany failed (%d)" % rc)
         for w, f, b in zip(part, fwd, bwd):
-            _split_cache[(id(w), False)] = (weakref.ref(w), w._version, w.data_ptr(), f, _images_epoch)
-            _split_cache[(id(w), True)] = (weakref.ref(w), w._version, w.data_ptr(), b, _images_epoch)
+            _split_cache.store((id(w), False), (w,), f)
+            _split_cache.store((id(w), True), (w,), b)
 
 
 def _split_fits(x, cout, upsample2x):
@@ -788,33 +791,10 @@ def conv3x3_split(x, weight, bias=None, act='none', slope=0.01, residual=None, u
         raise ValueError("unknown activation %r" % (act,))
     with torch.no_grad():
         key = _arm_range(id(weight), x.device)
-        y = _launch_split(x, _prepare_split(weight), bias.contiguous() if bias is not None else None, residual, weight.shape[0],
-                          act, slope, upsample2x)
+        y = _launch_lp("isrConv3x3ForwardSplit", x, _prepare_split(weight), bias.contiguous() if bias is not None else None, residual,
+                       weight.shape[0], act, slope, upsample2x)
         y._isr_range_key = key
         return y
-
-
-def _launch_split(x, wq, bias, residual, cout, act, slope, upsample2x, packed=False):
-    """One launch of isrConv3x3ForwardSplit (x: fp32 NCHW, channel planes may be padded; ``packed`` as in ``_launch_forward``)."""
-    lib = _sr()
-    x, xp, xi = _plane_strides(x)
-    fuse = False
-    if upsample2x:
-        fuse = bool(lib.isrConvF16SupportsUpsample(x.data_ptr(), x.shape[3], xp, xi))
-        if not fuse:          # unaligned low-res rows: the resize runs as its own kernel first
-            x, xp, xi = _plane_strides(bilinear_upsample2x(x))
-    n, cin = x.shape[0], x.shape[1]
-    h, w = (2 * x.shape[2], 2 * x.shape[3]) if fuse else (x.shape[2], x.shape[3])
-    rp = ri = 0
-    if residual is not None:
-        residual, rp, ri = _plane_strides(residual)
-    y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device) if packed else empty_planes(n, cout, h, w, x.device)
-    rc = lib.isrConv3x3ForwardSplit(_ptr(x), _ptr(wq), _ptr(bias), _ptr(residual), _ptr(y), n, cin, h, w, cout,
-                                    ACT_CODES[act], float(slope), 1 if fuse else 0, xp, xi, y.stride(1), cout * y.stride(1),
-                                    rp, ri, _stream())
-    if rc != 0:
-        raise RuntimeError("isrConv3x3ForwardSplit failed (%d)" % rc)
-    return y
 
 
 # ---- mixed-precision training mode (opt-in, NOT the parity path) ------------------------------------------------------
@@ -849,7 +829,7 @@ def _train_conv(x, weight, transpose_flip, bias, residual, act):
     flops = 2.0 * 9 * cin * cout * x.shape[0] * x.shape[2] * x.shape[3]
     if TRAIN_BF16 and cout > 8 and cin > 8 and tiles >= 256:
         _tally("bf16", flops)
-        return _launch_lp(x, _prepare_lp(weight, transpose_flip, True), bias, residual, cout, act, 0.0, False, True, packed=True)
+        return _launch_lp("isrConv3x3ForwardBf16", x, _prepare_lp(weight, transpose_flip, True), bias, residual, cout, act, 0.0, False, packed=True)
     # the split-operand kernel (fp32-equivalent accuracy, 2.3x the fp32 MFMA kernel) once a layer has enough 8x32-pixel
     # tiles to fill the persistent grid: the 64^2 / 128^2 post-block layers of a crop batch, 54 % of the step's flops
     # ... or, for a batch of small crops, enough 2-row tiles for the small-image form (conv3x3_split_rows2_kernel)
@@ -862,7 +842,7 @@ def _train_conv(x, weight, transpose_flip, bias, residual, act):
         slot = _gmax_slot(x.device, _GMAX_CONV_WORDS) if transpose_flip else None    # a data gradient: some layer's gz later on
         if slot is not None:
             _sr().isrSetMaxSlots(ctypes.c_void_p(slot), _GMAX_CONV_WORDS)
-        y = _launch_split(x, _prepare_split(weight, transpose_flip), bias, residual, cout, act, 0.0, False, packed=True)
+        y = _launch_lp("isrConv3x3ForwardSplit", x, _prepare_split(weight, transpose_flip), bias, residual, cout, act, 0.0, False, packed=True)
         if slot is not None:
             words = _sr().isrTakeMaxSlotWords()
             if words > 0:
@@ -1778,6 +1758,15 @@ def fill_flow_gbuffer(gbuffer_hwc, out=None, stream=None, threads=1024, one_laun
     return out
 
 
+def _shading_args(shading):
+    """(params[18], specular exponent, ao, inverse_ao, enable_specular) as the finishing kernels take them; ``shading`` None (no rgb
+    is asked for): a null ``params`` and the neutral values."""
+    if shading is None:
+        return None, 1, 0.0, 0, 0
+    return ((ctypes.c_float * 18)(*shading.packed_parameters()), int(shading._specular_exponent), float(shading._ao),
+            int(bool(shading.inverse_ao)), int(bool(shading.enable_specular)))
+
+
 def final_conv_finish(features, weight, bias, net_input, shading=None):
     """The network's last layer (64 -> 6, no activation) and ``finish_frame`` in one launch
     (``isrConvSmallFinishFrame``): features [1,Cin,4h,4w] (channel planes may be padded), net_input [1,>=5,h,w]
@@ -1790,15 +1779,9 @@ def final_conv_finish(features, weight, bias, net_input, shading=None):
     _, cin, H, W = features.shape
     h, w = H // 4, W // 4
     nxt = torch.empty((1, 6, H, W), dtype=torch.float32, device=features.device)
-    rgb, params = None, None
-    exponent, ao, inv, spec = 1, 0.0, 0, 0
-    if shading is not None:
-        rgb = torch.empty((1, 3, H, W), dtype=torch.float32, device=features.device)
-        params = (ctypes.c_float * 18)(*shading.packed_parameters())
-        exponent, ao = int(shading._specular_exponent), float(shading._ao)
-        inv, spec = int(bool(shading.inverse_ao)), int(bool(shading.enable_specular))
+    rgb = torch.empty((1, 3, H, W), dtype=torch.float32, device=features.device) if shading is not None else None
     rc = lib.isrConvSmallFinishFrame(_ptr(features), _ptr(w8), _ptr(b8), _ptr(net_input), _ptr(nxt), _ptr(rgb), cin, h, w, xp,
-                                     params, exponent, ao, inv, spec, _stream())
+                                     *_shading_args(shading), _stream())
     if rc != 0:
         raise RuntimeError("isrConvSmallFinishFrame failed (%d)" % rc)
     return nxt, rgb
@@ -1806,41 +1789,36 @@ def final_conv_finish(features, weight, bias, net_input, shading=None):
 
 # ---- the fused 1080p tail (csrc/sr_conv_tail.hip): postblock.6 + postblock.8 + frame finish without the 64-channel round trip ----
 TAIL_FUSION = True
-_tail_cache = {}
-_tail_ws = {}
+_tail_cache = _WeightImages(64)
+_tail_ws = {}                    # (device, h, w, stream, output channels) -> workspace of the fused tail
 
 
 def _prepare_tail(weight8):
     """The last layer's weights [6, 64, 3, 3] (colour networks: [3, 64, 3, 3]) by (tap, channel) row in the z stage's operand order,
     cached like ``prepare_weights``."""
     lib = _sr()
-    key = id(weight8)
-    hit = _tail_cache.get(key)
-    if hit is not None:
-        ref, version, ptr, wz, epoch = hit
-        if ref() is weight8 and version == weight8._version and ptr == weight8.data_ptr() and epoch == _images_epoch:
-            return wz
+    wz = _tail_cache.lookup(id(weight8), (weight8,))
+    if wz is not None:
+        return wz
     wz = torch.empty(lib.isrConvTailWeightBytes(), dtype=torch.uint8, device=weight8.device)
     prepare = lib.isrConvTailPrepare3 if weight8.shape[0] == 3 else lib.isrConvTailPrepare
     rc = prepare(_ptr(weight8.detach().contiguous()), _ptr(wz), _stream())
     if rc != 0:
         raise RuntimeError("isrConvTailPrepare failed (%d)" % rc)
-    if len(_tail_cache) > 64:
-        _tail_cache.clear()
-    _tail_cache[key] = (weakref.ref(weight8), weight8._version, weight8.data_ptr(), wz, _images_epoch)
+    _tail_cache.store(id(weight8), (weight8,), wz)
     return wz
 
 
 def tail_supported(features, weight6, weight8):
-    """Can ``tail_conv_finish`` take this frame?  (64 -> 64 -> 6 channels, one image, 16-byte aligned rows; the default
-    split-operand inference mode.)"""
+    """Can ``tail_conv_finish`` (64 -> 64 -> 6 channels) or ``tail_conv_finish_colour`` (64 -> 64 -> 3) take this frame?  (One image,
+    16-byte aligned rows; the default split-operand inference mode.)"""
     if not (TAIL_FUSION and SPLIT_F16 and not FAST_F16 and features.is_cuda and features.dtype == torch.float32):
         return False
     if any_hot(features.device):          # range guard: a layer of this model needs the exact kernels -- per-layer routing only
         return False
     if features.dim() != 4 or features.shape[0] != 1 or features.shape[1] != 64 or features.shape[2] % 4 or features.shape[3] % 4:
         return False
-    if tuple(weight6.shape) != (64, 64, 3, 3) or tuple(weight8.shape) != (6, 64, 3, 3):
+    if tuple(weight6.shape) != (64, 64, 3, 3) or tuple(weight8.shape) not in ((6, 64, 3, 3), (3, 64, 3, 3)):
         return False
     f, xp, _ = _plane_strides(features)
     return f is features and bool(_sr().isrConvTailSupported(_ptr(features), features.shape[2] // 4, features.shape[3] // 4, xp))
@@ -1856,6 +1834,14 @@ class PackedSplit:
     def __init__(self, data, channels, h, w, plane):
         self.data, self.channels, self.h, self.w, self.plane = data, channels, h, w, plane
         self.range_key = None      # range guard: the producer whose flag word describes these values
+
+    @classmethod
+    def empty(cls, channels, h, w, device, range_key=None):
+        """An uninitialised one for a producer to write (planes padded like the fp32 activations', ``plane_pad``)."""
+        plane = h * w + plane_pad(h, w)
+        out = cls(torch.empty(2 * (channels // 8) * plane * 4, dtype=torch.int32, device=device), channels, h, w, plane)
+        out.range_key = range_key
+        return out
 
     def to_float(self):
         """The fp32 tensor this stands for, hi + lo' 2^-11 (tests)."""
@@ -1876,15 +1862,11 @@ def conv3x3_split_packed(x, weight, bias=None, act='relu', slope=0.01, upsample2
     h, w = (2 * x.shape[2], 2 * x.shape[3]) if upsample2x else (x.shape[2], x.shape[3])
     if upsample2x and not lib.isrConvF16SupportsUpsample(x.data_ptr(), x.shape[3], xp, cin * xp):
         raise ValueError("conv3x3_split_packed: the fused upsampling needs 16-byte aligned low-resolution rows")
-    plane = h * w + plane_pad(h, w)
-    data = torch.empty(2 * (cout // 8) * plane * 4, dtype=torch.int32, device=x.device)
-    key = _arm_range(id(weight), x.device)
+    out = PackedSplit.empty(cout, h, w, x.device, range_key=_arm_range(id(weight), x.device))
     rc = lib.isrConv3x3ForwardSplitPacked(_ptr(x), _ptr(_prepare_split(weight)), _ptr(bias.detach().contiguous() if bias is not None else None),
-                                          _ptr(data), cin, h, w, cout, ACT_CODES[act], float(slope), 1 if upsample2x else 0, xp, plane, _stream())
+                                          _ptr(out.data), cin, h, w, cout, ACT_CODES[act], float(slope), 1 if upsample2x else 0, xp, out.plane, _stream())
     if rc != 0:
         raise RuntimeError("isrConv3x3ForwardSplitPacked failed (%d)" % rc)
-    out = PackedSplit(data, cout, h, w, plane)
-    out.range_key = key
     return out
 
 
@@ -1898,25 +1880,20 @@ def conv3x3_split_from_packed(xp, weight, bias=None, act='none', slope=0.01, res
     rp = 0
     if residual is not None:
         residual, rp, _ = _plane_strides(residual)
+    key = _arm_range(id(weight), xp.data.device)
     if packed_out:
         assert residual is None and cout % 8 == 0
-        plane = h * w + plane_pad(h, w)
-        out = torch.empty(2 * (cout // 8) * plane * 4, dtype=torch.int32, device=xp.data.device)
-        yplane = plane
+        out = PackedSplit.empty(cout, h, w, xp.data.device, range_key=key)
+        y, yplane = out.data, out.plane
     else:
-        out = empty_planes(1, cout, h, w, xp.data.device)
+        out = y = empty_planes(1, cout, h, w, xp.data.device)
+        out._isr_range_key = key
         yplane = out.stride(1)
-    key = _arm_range(id(weight), xp.data.device)
     rc = lib.isrConv3x3ForwardSplitFromPacked(_ptr(xp.data), _ptr(_prepare_split(weight)), _ptr(bias.detach().contiguous() if bias is not None else None),
-                                              _ptr(residual), _ptr(out), 1 if packed_out else 0, cin, h, w, cout, ACT_CODES[act], float(slope),
+                                              _ptr(residual), _ptr(y), 1 if packed_out else 0, cin, h, w, cout, ACT_CODES[act], float(slope),
                                               xp.plane, yplane, rp, _stream())
     if rc != 0:
         raise RuntimeError("isrConv3x3ForwardSplitFromPacked failed (%d)" % rc)
-    if packed_out:
-        out = PackedSplit(out, cout, h, w, yplane)
-        out.range_key = key
-    else:
-        out._isr_range_key = key
     return out
 
 
@@ -1931,28 +1908,22 @@ def conv3x3_split_from_packed(xp, weight, bias=None, act='none', slope=0.01, res
 # roofline's peak is priced at), the operand DMA adds 0.08 ms of LDS write traffic beside 0.67 LDS reads per MFMA, and the four
 # epilogues per tile with their stride-2 pixel stores 0.17 ms; the interpolating kernel was never more than 35 % above that floor.
 UPS_PHASE = os.environ.get("ISR_UPS_PHASE", "0") == "1"
-_upsp_cache = {}
+_upsp_cache = _WeightImages(64)
 
 
 def _prepare_ups_phase(weight):
     """The stacked image of the four effective weight sets of a [64, 64, 3, 3] weight (``isrConvUpsPhasePrepare``), cached per weight version."""
     lib = _sr()
-    key = id(weight)
-    hit = _upsp_cache.get(key)
-    if hit is not None:
-        ref, version, ptr, wq, epoch = hit
-        if ref() is weight and version == weight._version and ptr == weight.data_ptr() and epoch == _images_epoch:
-            return wq
+    wq = _upsp_cache.lookup(id(weight), (weight,))
+    if wq is not None:
+        return wq
     w = weight.detach().contiguous()
     wq = torch.empty(lib.isrConvUpsPhaseWeightBytes(), dtype=torch.uint8, device=weight.device)
     scratch = torch.empty(lib.isrConvUpsPhaseScratchBytes(), dtype=torch.uint8, device=weight.device)
     rc = lib.isrConvUpsPhasePrepare(_ptr(w), _ptr(wq), _ptr(scratch), _stream())
     if rc != 0:
         raise RuntimeError("isrConvUpsPhasePrepare failed (%d)" % rc)
-    if len(_upsp_cache) > 64:
-        for k in [k for k, v in _upsp_cache.items() if v[0]() is None]:
-            del _upsp_cache[k]
-    _upsp_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wq, _images_epoch)
+    _upsp_cache.store(id(weight), (weight,), wq)
     return wq
 
 
@@ -1961,13 +1932,10 @@ def pack_split(x):
     x, xp, _ = _plane_strides(x)
     _, c, h, w = x.shape
     assert x.shape[0] == 1 and c % 8 == 0
-    plane = h * w + plane_pad(h, w)
-    data = torch.empty(2 * (c // 8) * plane * 4, dtype=torch.int32, device=x.device)
-    rc = _sr().isrPackSplit(_ptr(x), _ptr(data), c, h, w, xp, plane, _stream())
+    out = PackedSplit.empty(c, h, w, x.device, range_key=getattr(x, '_isr_range_key', None))
+    rc = _sr().isrPackSplit(_ptr(x), _ptr(out.data), c, h, w, xp, out.plane, _stream())
     if rc != 0:
         raise RuntimeError("isrPackSplit failed (%d)" % rc)
-    out = PackedSplit(data, c, h, w, plane)
-    out.range_key = getattr(x, '_isr_range_key', None)
     return out
 
 
@@ -1985,18 +1953,12 @@ def conv3x3_ups_phase(xp, weight, bias=None, act='relu', slope=0.01):
     """act(conv3x3(U2(x), weight) + bias) of a packed-split x [64, h, w] -> packed-split [64, 2h, 2w] (``isrConvUpsPhase``)."""
     lib = _sr()
     assert isinstance(xp, PackedSplit) and xp.channels == 64 and tuple(weight.shape) == (64, 64, 3, 3)
-    H, W = 2 * xp.h, 2 * xp.w
-    plane = H * W + plane_pad(H, W)
-    dev = xp.data.device
-    data = torch.empty(2 * 8 * plane * 4, dtype=torch.int32, device=dev)
     wq = _prepare_ups_phase(weight)
-    key = _arm_range(id(weight), dev)
+    out = PackedSplit.empty(64, 2 * xp.h, 2 * xp.w, xp.data.device, range_key=_arm_range(id(weight), xp.data.device))
     rc = lib.isrConvUpsPhase(_ptr(xp.data), _ptr(wq), _ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous() if bias is not None else None),
-                             _ptr(data), xp.h, xp.w, ACT_CODES[act], float(slope), xp.plane, plane, _stream())
+                             _ptr(out.data), xp.h, xp.w, ACT_CODES[act], float(slope), xp.plane, out.plane, _stream())
     if rc != 0:
         raise RuntimeError("isrConvUpsPhase failed (%d)" % rc)
-    out = PackedSplit(data, 64, H, W, plane)
-    out.range_key = key
     return out
 
 
@@ -2015,16 +1977,16 @@ def packed_supported(x, weight, upsample2x):
     return (not upsample2x) or bool(_sr().isrConvF16SupportsUpsample(x.data_ptr(), x.shape[3], xp, x.shape[1] * xp))
 
 
-def tail_conv_finish(features, weight6, bias6, weight8, bias8, net_input, shading=None, out=None):
-    """features [1,64,4h,4w] (the output of postblock.4; channel planes may be padded) -> relu(conv3x3(., weight6) + bias6)
-    -> conv3x3(., weight8) + bias8 -> ``finish_frame``: (next_prev [1,6,4h,4w], rgb [1,3,4h,4w] or None) in two launches
-    (``isrConvTailFinishFrame``); the 64-channel tensor between the two convolutions never exists in memory.
-    ``out``: (next_prev, rgb) tensors to write into (the frame graph's static output buffers)."""
+def _tail_operands(features, weight6, bias6, weight8, bias8, net_input, cout):
+    """What ``tail_conv_finish`` (``cout`` 6) and ``tail_conv_finish_colour`` (3) do alike, everything up to the output tensors:
+    -> (features are packed-split?, device, H, W, plane stride of the features, the library call's seven leading tensors).  Arms
+    the range flag: the caller launches next, with nothing but allocations in between."""
     lib = _sr()
     packed = isinstance(features, PackedSplit)
     if packed:
         H, W, xp, dev = features.h, features.w, features.plane, features.data.device
         assert features.channels == 64
+        features = features.data
     else:
         features, xp, _ = _plane_strides(features)
         _, _, H, W = features.shape
@@ -2033,27 +1995,32 @@ def tail_conv_finish(features, weight6, bias6, weight8, bias8, net_input, shadin
     h, w = H // 4, W // 4
     wq6 = _prepare_split(weight6)
     wz = _prepare_tail(weight8)
-    key = (dev, h, w, torch.cuda.current_stream().cuda_stream)
+    key = (dev, h, w, torch.cuda.current_stream().cuda_stream, cout)
     ws = _tail_ws.get(key)
     if ws is None:
-        ws = torch.empty(lib.isrConvTailWorkspaceBytes(h, w), dtype=torch.uint8, device=dev)
+        ws = torch.empty((lib.isrConvTailWorkspaceBytes3 if cout == 3 else lib.isrConvTailWorkspaceBytes)(h, w), dtype=torch.uint8, device=dev)
         _tail_ws[key] = ws
+    b6 = bias6.detach().contiguous() if bias6 is not None else None
+    b8 = bias8.detach().contiguous() if bias8 is not None else torch.zeros(cout, dtype=torch.float32, device=dev)
+    _arm_range(("tail", id(weight6)), dev, members=[id(weight6)])         # the largest |y6|: the intermediate is split in registers inside the kernel
+    return packed, dev, H, W, xp, (features, wq6, b6, wz, b8, ws, net_input)
+
+
+def tail_conv_finish(features, weight6, bias6, weight8, bias8, net_input, shading=None, out=None):
+    """features [1,64,4h,4w] (the output of postblock.4; channel planes may be padded) -> relu(conv3x3(., weight6) + bias6)
+    -> conv3x3(., weight8) + bias8 -> ``finish_frame``: (next_prev [1,6,4h,4w], rgb [1,3,4h,4w] or None) in two launches
+    (``isrConvTailFinishFrame``); the 64-channel tensor between the two convolutions never exists in memory.
+    ``out``: (next_prev, rgb) tensors to write into (the frame graph's static output buffers)."""
+    lib = _sr()
+    packed, dev, H, W, xp, operands = _tail_operands(features, weight6, bias6, weight8, bias8, net_input, 6)
     nxt = out[0] if out is not None else torch.empty((1, 6, H, W), dtype=torch.float32, device=dev)
     assert tuple(nxt.shape) == (1, 6, H, W) and nxt.is_contiguous() and nxt.dtype == torch.float32
-    rgb, params = None, None
-    exponent, ao, inv, spec = 1, 0.0, 0, 0
+    rgb = None
     if shading is not None:
         rgb = out[1] if out is not None else torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
         assert tuple(rgb.shape) == (1, 3, H, W) and rgb.is_contiguous()
-        params = (ctypes.c_float * 18)(*shading.packed_parameters())
-        exponent, ao = int(shading._specular_exponent), float(shading._ao)
-        inv, spec = int(bool(shading.inverse_ao)), int(bool(shading.enable_specular))
-    b6 = bias6.detach().contiguous() if bias6 is not None else None
-    b8 = bias8.detach().contiguous() if bias8 is not None else torch.zeros(6, dtype=torch.float32, device=dev)
-    _arm_range(("tail", id(weight6)), dev, members=[id(weight6)])         # the largest |y6|: the intermediate is split in registers inside the kernel
     fn = lib.isrConvTailFinishFramePacked if packed else lib.isrConvTailFinishFrame
-    rc = fn(_ptr(features.data if packed else features), _ptr(wq6), _ptr(b6), _ptr(wz), _ptr(b8), _ptr(ws), _ptr(net_input), _ptr(nxt), _ptr(rgb),
-                                    h, w, xp, params, exponent, ao, inv, spec, _stream())
+    rc = fn(*map(_ptr, operands), _ptr(nxt), _ptr(rgb), H // 4, W // 4, xp, *_shading_args(shading), _stream())
     if rc != 0:
         raise RuntimeError("isrConvTailFinishFrame failed (%d)" % rc)
     return nxt, rgb
@@ -2067,16 +2034,8 @@ def finish_frame(raw, net_input, shading=None):
     _, _, H, W = raw.shape
     h, w = H // 4, W // 4
     nxt = torch.empty_like(raw)
-    rgb = None
-    params = None
-    exponent, ao, inv, spec = 1, 0.0, 0, 0
-    if shading is not None:
-        rgb = torch.empty((1, 3, H, W), dtype=torch.float32, device=raw.device)
-        vals = shading.packed_parameters()
-        params = (ctypes.c_float * 18)(*vals)
-        exponent, ao = int(shading._specular_exponent), float(shading._ao)
-        inv, spec = int(bool(shading.inverse_ao)), int(bool(shading.enable_specular))
-    rc = _sr().isrFinishFrame(_ptr(raw), _ptr(net_input), _ptr(nxt), _ptr(rgb), h, w, params, exponent, ao, inv, spec, _stream())
+    rgb = torch.empty((1, 3, H, W), dtype=torch.float32, device=raw.device) if shading is not None else None
+    rc = _sr().isrFinishFrame(_ptr(raw), _ptr(net_input), _ptr(nxt), _ptr(rgb), h, w, *_shading_args(shading), _stream())
     if rc != 0:
         raise RuntimeError("isrFinishFrame failed (%d)" % rc)
     return nxt, rgb
@@ -2148,55 +2107,18 @@ def final_conv_finish_colour(features, weight, bias, net_input):
     return out
 
 
-def tail_supported_colour(features, weight6, weight8):
-    """``tail_supported`` for a colour network: 64 -> 64 -> 3 channels."""
-    if not (TAIL_FUSION and SPLIT_F16 and not FAST_F16 and features.is_cuda and features.dtype == torch.float32):
-        return False
-    if any_hot(features.device):          # range guard: a layer of this model needs the exact kernels -- per-layer routing only
-        return False
-    if features.dim() != 4 or features.shape[0] != 1 or features.shape[1] != 64 or features.shape[2] % 4 or features.shape[3] % 4:
-        return False
-    if tuple(weight6.shape) != (64, 64, 3, 3) or tuple(weight8.shape) != (3, 64, 3, 3):
-        return False
-    f, xp, _ = _plane_strides(features)
-    return f is features and bool(_sr().isrConvTailSupported(_ptr(features), features.shape[2] // 4, features.shape[3] // 4, xp))
-
-
-_tail_ws_colour = {}
-
-
 def tail_conv_finish_colour(features, weight6, bias6, weight8, bias8, net_input, out=None):
     """``tail_conv_finish`` for a colour network: features [1,64,4h,4w] (fp32, or a ``PackedSplit``) -> relu(conv3x3(., weight6) +
     bias6) -> conv3x3(., weight8 [3,64,3,3]) + bias8 -> ``finish_frame_colour``, in two launches (``isrConvTailFinishFrame3``): nine
     S planes and 27 rows of the extra product instead of eighteen and 54.  Returns [1,3,4h,4w] (``out`` to write into)."""
     lib = _sr()
-    packed = isinstance(features, PackedSplit)
-    if packed:
-        H, W, xp, dev = features.h, features.w, features.plane, features.data.device
-        assert features.channels == 64
-    else:
-        features, xp, _ = _plane_strides(features)
-        _, _, H, W = features.shape
-        dev = features.device
     assert tuple(weight8.shape) == (3, 64, 3, 3) and net_input.shape[1] >= 3
-    net_input = net_input.contiguous()
-    h, w = H // 4, W // 4
-    wq6 = _prepare_split(weight6)
-    wz = _prepare_tail(weight8)
-    key = (dev, h, w, torch.cuda.current_stream().cuda_stream)
-    ws = _tail_ws_colour.get(key)
-    if ws is None:
-        ws = torch.empty(lib.isrConvTailWorkspaceBytes3(h, w), dtype=torch.uint8, device=dev)
-        _tail_ws_colour[key] = ws
+    packed, dev, H, W, xp, operands = _tail_operands(features, weight6, bias6, weight8, bias8, net_input, 3)
     if out is None:
         out = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
     assert tuple(out.shape) == (1, 3, H, W) and out.is_contiguous() and out.dtype == torch.float32
-    b6 = bias6.detach().contiguous() if bias6 is not None else None
-    b8 = bias8.detach().contiguous() if bias8 is not None else torch.zeros(3, dtype=torch.float32, device=dev)
-    _arm_range(("tail", id(weight6)), dev, members=[id(weight6)])         # the largest |y6|: the intermediate is split in registers inside the kernel
     fn = lib.isrConvTailFinishFrame3Packed if packed else lib.isrConvTailFinishFrame3
-    rc = fn(_ptr(features.data if packed else features), _ptr(wq6), _ptr(b6), _ptr(wz), _ptr(b8), _ptr(ws), _ptr(net_input), _ptr(out),
-            h, w, xp, _stream())
+    rc = fn(*map(_ptr, operands), _ptr(out), H // 4, W // 4, xp, _stream())
     if rc != 0:
         raise RuntimeError("isrConvTailFinishFrame3 failed (%d)" % rc)
     return out

@@ -33,29 +33,49 @@ def default_shading(device, fov=30.0):
     return sh
 
 
+def _walk_to_tail(net, x, after_trunk, prefetch_point, last_shape, packed_tail):
+    """The part of the network every fused frame walks alike: dataflow trunk -> postblock.1 -> postblock.4, up to the input of the
+    fused tail.  -> (f4, after_trunk, f2): f4 an fp32 tensor or an ``ops.PackedSplit``, or None when the tail is not this frame's route
+    (switched off, a layer on the range guard's exact route, a last layer other than ``last_shape``) and nothing was enqueued;
+    ``after_trunk`` as given if it is still to be called, else None (it ran at ``prefetch_point``); f2, postblock.1's output, for
+    the caller to hold until the frame's last launch is enqueued (its memory goes back to the allocator at the end of the frame,
+    not under the tail's output allocations).  ``packed_tail``: passed on to ``forward_features`` (the phase-decomposed
+    upsampling layers, which only the unshaded networks take)."""
+    last, six, four = net.postblock[8], net.postblock[6], net.postblock[4]
+    if not (ops.TAIL_FUSION and ops.SPLIT_F16 and not ops.FAST_F16 and not ops.any_hot(x.device)
+            and tuple(six.weight.shape) == (64, 64, 3, 3) and tuple(last.weight.shape) == last_shape):
+        return None, after_trunk, None
+    f2 = net.forward_features(x, last_three=False, after_trunk=after_trunk if prefetch_point == "trunk" else None, packed_tail=packed_tail)
+    if prefetch_point == "trunk":
+        after_trunk = None
+    if prefetch_point == "ups1" and after_trunk is not None:
+        after_trunk(); after_trunk = None
+    if isinstance(f2, ops.PackedSplit):
+        # the phase-decomposed route (csrc/sr_conv_upsp.h): trunk -> postblock.1 -> postblock.4 -> tail, packed-split all the way
+        if not ops.ups_phase_supported(f2, four.weight):
+            raise RuntimeError("run_network: postblock.4 does not take the packed-split tensor postblock.1 produced")
+        f4 = ops.conv3x3_ups_phase(f2, four.weight, four.bias, act='relu')
+    elif ops.packed_supported(f2, four.weight, True):
+        # postblock.4 writes its output packed-split (already the (hi, lo') units postblock.6 multiplies), the tail
+        # stages them by LDS-DMA: no conversion on the way in, no LDS transposition on the way out
+        f4 = ops.conv3x3_split_packed(f2, four.weight, four.bias, act='relu', upsample2x=True)
+    else:
+        f4 = ops.conv3x3(f2, four.weight, four.bias, act='relu', upsample2x=True)
+    if after_trunk is not None and prefetch_point != "tail":
+        after_trunk(); after_trunk = None                # "ups2": beside the fused tail
+    return f4, after_trunk, f2
+
+
 def run_network_colour(model, x, after_trunk=None, prefetch_point="trunk"):
     """``run_network`` for a colour model: input [1,c+48,h,w] -> the frame [1,3,4h,4w], clamp(prediction, 0, 1) -- the displayed RGB
     and the next frame's ``prev_high`` in one tensor.  The same routing: dataflow trunk -> postblock.1 -> postblock.4 (packed-split
-    where ``ops.packed_supported``) -> the three-channel fused tail (``ops.tail_conv_finish_colour``); with a layer on the range
-    guard's exact route, the per-layer kernels and the small-Cout last layer with the colour finishing in its epilogue."""
+    where ``ops.packed_supported``) -> the three-channel fused tail (``ops.tail_conv_finish_colour`` where ``ops.tail_supported``);
+    with a layer on the range guard's exact route, the per-layer kernels and the small-Cout last layer with the colour finishing in
+    its epilogue."""
     net = model.model
-    last, six, four = net.postblock[8], net.postblock[6], net.postblock[4]
-    tail = ops.TAIL_FUSION and ops.SPLIT_F16 and not ops.FAST_F16 and not ops.any_hot(x.device) \
-        and tuple(six.weight.shape) == (64, 64, 3, 3) and tuple(last.weight.shape) == (3, 64, 3, 3)
-    f4 = None
-    if tail:
-        f2 = net.forward_features(x, last_three=False, after_trunk=after_trunk if prefetch_point == "trunk" else None)
-        if prefetch_point in ("trunk", "ups1"):
-            if prefetch_point == "ups1" and after_trunk is not None:
-                after_trunk()
-            after_trunk = None
-        if ops.packed_supported(f2, four.weight, True):
-            f4 = ops.conv3x3_split_packed(f2, four.weight, four.bias, act='relu', upsample2x=True)
-        else:
-            f4 = ops.conv3x3(f2, four.weight, four.bias, act='relu', upsample2x=True)
-        if after_trunk is not None and prefetch_point != "tail":
-            after_trunk(); after_trunk = None                # "ups2": beside the fused tail
-    if isinstance(f4, ops.PackedSplit) or (f4 is not None and ops.tail_supported_colour(f4, six.weight, last.weight)):
+    last, six = net.postblock[8], net.postblock[6]
+    f4, after_trunk, _f2 = _walk_to_tail(net, x, after_trunk, prefetch_point, (3, 64, 3, 3), packed_tail=False)
+    if isinstance(f4, ops.PackedSplit) or (f4 is not None and ops.tail_supported(f4, six.weight, last.weight)):
         frame = ops.tail_conv_finish_colour(f4, six.weight, six.bias, last.weight, last.bias, x)
     elif f4 is not None:
         f6 = ops.conv3x3(f4, six.weight, six.bias, act='relu')
@@ -77,34 +97,9 @@ def run_network(model, shading, x, after_trunk=None, prefetch_point="trunk", out
     while ``out`` was given: the frame graph then stays off)."""
     net = model.model
     shading.inverse_ao = model.inverse_ao
-    last = net.postblock[8]
-    six = net.postblock[6]
-    f4 = None
-    tail = last.weight.shape[0] == 6 and ops.TAIL_FUSION and ops.SPLIT_F16 and not ops.FAST_F16 and not ops.any_hot(x.device)
-    four = net.postblock[4]
-    if tail and ops.TAIL_PACKED and tuple(six.weight.shape) == (64, 64, 3, 3) and tuple(last.weight.shape) == (6, 64, 3, 3):
-        at = prefetch_point
-        f2 = net.forward_features(x, last_three=False, after_trunk=after_trunk if at == "trunk" else None, packed_tail=True)
-        if at == "trunk":
-            after_trunk = None
-        if at == "ups1" and after_trunk is not None:
-            after_trunk(); after_trunk = None
-        if isinstance(f2, ops.PackedSplit):
-            # the phase-decomposed route (csrc/sr_conv_upsp.h): trunk -> postblock.1 -> postblock.4 -> tail, packed-split all the way
-            if not ops.ups_phase_supported(f2, four.weight):
-                raise RuntimeError("run_network: postblock.4 does not take the packed-split tensor postblock.1 produced")
-            f4 = ops.conv3x3_ups_phase(f2, four.weight, four.bias, act='relu')
-        elif ops.packed_supported(f2, four.weight, True):
-            # postblock.4 writes its output packed-split (already the (hi, lo') units postblock.6 multiplies), the tail
-            # stages them by LDS-DMA: no conversion on the way in, no LDS transposition on the way out
-            f4 = ops.conv3x3_split_packed(f2, four.weight, four.bias, act='relu', upsample2x=True)
-        else:
-            f4 = ops.conv3x3(f2, four.weight, four.bias, act='relu', upsample2x=True)
-    elif tail:
-        f4 = net.forward_features(x, last_two=False, after_trunk=after_trunk)
-        after_trunk = None
-    if f4 is not None and after_trunk is not None and prefetch_point != "tail":
-        after_trunk(); after_trunk = None                # "ups2": beside the fused tail
+    last, six = net.postblock[8], net.postblock[6]
+    # (ISR_TAIL_PACKED=0: ``ops.packed_supported`` refuses, postblock.4 runs per layer and hands the tail an fp32 tensor)
+    f4, after_trunk, _f2 = _walk_to_tail(net, x, after_trunk, prefetch_point, (6, 64, 3, 3), packed_tail=ops.TAIL_PACKED)
     if isinstance(f4, ops.PackedSplit) or (f4 is not None and ops.tail_supported(f4, six.weight, last.weight)):
         # postblock.6, postblock.8 and the frame's finishing in two launches; the 64-channel 1080p tensor between the
         # two convolutions never goes to memory (csrc/sr_conv_tail.hip)

@@ -106,7 +106,7 @@ def test_colour_tail_matches_the_three_kernel_path_and_fp64(h, w):
     """The criterion of test_tail_gpu.py::test_tail_matches_the_three_kernel_path_and_fp64, for three output channels."""
     from isosurfacesuperresolution_amd import ops
     f4, w6, b6, w8, b8, x = _tail_setup(h, w, seed=h * 100 + w)
-    assert ops.tail_supported_colour(f4, w6, w8)
+    assert ops.tail_supported(f4, w6, w8)
     with torch.no_grad():
         out_t = ops.tail_conv_finish_colour(f4, w6, b6, w8, b8, x)
         f6 = ops.conv3x3(f4, w6, b6, act='relu')

@@ -795,3 +795,52 @@ def test_prefetched_composite_hands_out_frames_in_request_order_on_the_cpu():
     f = src.take(0).clone()
     assert calls == [5, 0, 0]
     assert torch.equal(d, c) and torch.equal(e, a) and torch.equal(f, a)
+
+
+def test_weight_image_cache_validity_and_eviction():
+    """ops._WeightImages, the one cache behind every ``ops._prepare_*``: an image is handed out while the very same live tensor has the
+    version and address it was made from and ``invalidate_weight_images()`` has not been called; beyond its cap the cache drops the
+    entries of DEAD tensors only (a captured frame or a launch in flight may still read a live one's image)."""
+    from isosurfacesuperresolution_amd import ops
+    cache = ops._WeightImages(cap=4)
+    w, b = torch.zeros(6, 4, 3, 3), torch.zeros(6)
+    assert cache.lookup(id(w), (w,)) is None
+    cache.store(id(w), (w,), "image")
+    assert cache.lookup(id(w), (w,)) == "image"
+    w.add_(1.0)                                                    # a change autograd sees
+    assert cache.lookup(id(w), (w,)) is None
+    # (weight, bias) entries watch the bias as well; a bias of None is a value like any other
+    cache.store("wb", (w, b), "with bias")
+    cache.store("w-", (w, None), "without")
+    assert cache.lookup("wb", (w, b)) == "with bias" and cache.lookup("w-", (w, None)) == "without"
+    assert cache.lookup("w-", (w, b)) is None and cache.lookup("wb", (w, None)) is None
+    b.add_(1.0)
+    assert cache.lookup("wb", (w, b)) is None and cache.lookup("w-", (w, None)) == "without"
+    # a change behind autograd's back: the epoch
+    cache.store("wb", (w, b), "again")
+    assert cache.lookup("wb", (w, b)) == "again"
+    ops.invalidate_weight_images()
+    assert cache.lookup("wb", (w, b)) is None and cache.lookup("w-", (w, None)) is None
+    # another tensor under the key of one that died (ids are recycled), equal in version and shape
+    cache.clear()
+    a = torch.zeros(2, 2, 3, 3)
+    key = id(a)
+    cache.store(key, (a,), "a's image")
+    del a
+    other = torch.zeros(2, 2, 3, 3)
+    assert cache.lookup(key, (other,)) is None
+    # more live weights than the cap: none of them is dropped; the dead ones go with the next store
+    cache.clear()
+    live = [torch.zeros(1, 1, 3, 3) for _ in range(7)]
+    dead = [torch.zeros(1, 1, 3, 3) for _ in range(3)]
+    for k, t in enumerate(dead):
+        cache.store(("dead", k), (t,), -k)
+    for k, t in enumerate(live):
+        cache.store(("live", k), (t,), k)
+    assert len(cache.entries) > cache.cap and all(cache.lookup(("live", k), (t,)) == k for k, t in enumerate(live))
+    del dead                                                       # (the loop variable has moved on to a live tensor)
+    extra = torch.zeros(1, 1, 3, 3)
+    cache.store("extra", (extra,), "x")
+    assert not any(key[0] == "dead" for key in cache.entries if isinstance(key, tuple))
+    assert all(cache.lookup(("live", k), (t,)) == k for k, t in enumerate(live)) and cache.lookup("extra", (extra,)) == "x"
+    assert len(cache.entries) == len(live) + 1
