@@ -421,6 +421,43 @@ void isrSetTrunkPackedResult(int on);      /* 1: isrTrunkDataflow also writes th
  * Environment: ISR_TRUNK_ROWS. */
 void isrSetTrunkRows(int rows);
 
+/* The DISPLAY STAGE of the viewer's frame in one launch (csrc/sr_display.hip), per high-resolution pixel: what the reference viewer does
+ * between the network and the window (SuperresolutionNetwork/mainGUI.py:603-608,626-636,762-853) -- the twelve-channel image (x4
+ * bilinear of the low G-buffer with the network's channels in place), background masking, the focus-of-context blend with a
+ * full-resolution G-buffer (shaded here), the channel view, the temporal post-smoothing against the warped previous DISPLAYED image, and
+ * an 8-bit RGBA copy.  The arithmetic is that of isosurfacesuperresolution_amd/viewer.py: compose_display, operation by operation (no
+ * contraction): the same bits wherever no shading enters, 1e-4 where the focus window is shaded (as isrFinishFrame against the module path).
+ * All pointers are device pointers; optional parts are NULL.  H = 4 h, W = 4 w.  Returns 0 ok, -1 bad arguments, -2 launch failure. */
+#define ISR_VIEW_COLOR 0
+#define ISR_VIEW_MASK 1
+#define ISR_VIEW_NORMAL 2
+#define ISR_VIEW_DEPTH 3
+#define ISR_VIEW_AO 4
+#define ISR_VIEW_FLOW 5
+typedef struct IsrDisplayParams {
+    const float* gbuffer;       /* [h][w][12] the renderer's low-resolution G-buffer of the frame (mask in [0, 1]) */
+    const float* rgb;           /* [3][H][W] the frame's colour: the shaded network output, or a colour network's clamped prediction */
+    const float* raw;           /* [6][H][W] mask, normal, depth, AO as the network left them (clamped / normalised); NULL: a colour network */
+    const float* flow;          /* [2][h][w] hole-filled flow of the frame (isrFlowFill); needed by ISR_VIEW_FLOW and with `prev` */
+    const float* prev;          /* [3][H][W] the previous displayed image, or NULL: no post-smoothing.  Must not be `out` */
+    const float* focus;         /* [H][W][12] full-resolution G-buffer of the same camera (read inside `viewport` where focus_mask > 0), or NULL */
+    const float* focus_mask;    /* [H][W] blend weight of the focus window, 1 = full-resolution render; with `focus` */
+    const float* depth_bounds;  /* [2] (min, max) depth of the frame; ISR_VIEW_DEPTH */
+    float* out;                 /* [3][H][W] the displayed image */
+    unsigned char* out8;        /* [H][W][4] RGBA, round(clamp(out, 0, 1) * 255), A = 255; or NULL.  4-byte aligned */
+    int h, w;
+    int channel;                /* ISR_VIEW_* */
+    int masking;                /* 1: image = background0 + (base_mask / 2 + 1 / 2) (image - background0) */
+    float background0;
+    float smooth_prev, smooth_cur;      /* out = smooth_prev * warp(prev) + smooth_cur * image (with `prev`) */
+    int viewport[4];            /* minX, minY, maxX, maxY of the focus window in high-resolution pixels (max exclusive) */
+    float shading[18];          /* ambient, diffuse, specular, light, material, background (utils.ScreenSpaceShading.packed_parameters) */
+    int exponent;
+    float ao_strength;
+    int enable_specular;
+} IsrDisplayParams;
+int isrDisplayFrame(const IsrDisplayParams* params, void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

@@ -17,6 +17,7 @@ import os
 import warnings
 import weakref
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -32,6 +33,14 @@ def _warn_once(key, message):
     if key not in _warned:
         _warned.add(key)
         warnings.warn(message, RuntimeWarning, stacklevel=3)
+
+
+class _DisplayParams(ctypes.Structure):
+    """``IsrDisplayParams`` of include/isr_sr_kernels.h."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("gbuffer", "rgb", "raw", "flow", "prev", "focus", "focus_mask", "depth_bounds", "out", "out8")] + [
+        ("h", ctypes.c_int), ("w", ctypes.c_int), ("channel", ctypes.c_int), ("masking", ctypes.c_int), ("background0", ctypes.c_float),
+        ("smooth_prev", ctypes.c_float), ("smooth_cur", ctypes.c_float), ("viewport", ctypes.c_int * 4), ("shading", ctypes.c_float * 18),
+        ("exponent", ctypes.c_int), ("ao_strength", ctypes.c_float), ("enable_specular", ctypes.c_int)]
 
 
 def _bind(lib):
@@ -143,6 +152,8 @@ def _bind(lib):
     lib.isrSetRangeFlag.argtypes = [vp]; lib.isrSetRangeFlag.restype = None
     lib.isrSetTrunkErrorWord.argtypes = [vp]; lib.isrSetTrunkErrorWord.restype = None
     lib.isrSetTrunkRows.argtypes = [ci]; lib.isrSetTrunkRows.restype = None
+    if hasattr(lib, "isrDisplayFrame"):               # (an older build loaded through ISR_SR_LIB for an A/B run has no display stage)
+        lib.isrDisplayFrame.argtypes = [ctypes.POINTER(_DisplayParams), vp]; lib.isrDisplayFrame.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -2121,4 +2132,87 @@ def tail_conv_finish_colour(features, weight6, bias6, weight8, bias8, net_input,
     rc = fn(*map(_ptr, operands), _ptr(out), H // 4, W // 4, xp, _stream())
     if rc != 0:
         raise RuntimeError("isrConvTailFinishFrame3 failed (%d)" % rc)
+    return out
+
+
+# ---- the viewer's display stage (viewer.py) --------------------------------------------------------------------------------------------
+DISPLAY_VIEWS = {"color": 0, "mask": 1, "normal": 2, "depth": 3, "ao": 4, "flow": 5}       # ISR_VIEW_*
+
+
+def display_supported(gbuffer_hwc, rgb, raw=None):
+    """Can ``display_frame`` take these tensors: fp32 on the device, a [h,w,12] G-buffer, rgb [1,3,4h,4w], raw None or [1,6,4h,4w]?"""
+    if not (gbuffer_hwc.is_cuda and rgb.is_cuda and gbuffer_hwc.dtype == torch.float32 and rgb.dtype == torch.float32):
+        return False
+    if gbuffer_hwc.dim() != 3 or gbuffer_hwc.shape[-1] != 12 or not gbuffer_hwc.is_contiguous():
+        return False
+    h, w = gbuffer_hwc.shape[0], gbuffer_hwc.shape[1]
+    if not (0 < h <= 16383 and 0 < w <= 16383) or tuple(rgb.shape) != (1, 3, 4 * h, 4 * w):
+        return False
+    return raw is None or (raw.is_cuda and raw.dtype == torch.float32 and tuple(raw.shape) == (1, 6, 4 * h, 4 * w))
+
+
+def display_frame(gbuffer_hwc, rgb, raw=None, filled_flow=None, shading=None, channel="color", masking=False, background0=1.0, focus=None,
+                  focus_gbuffer=None, bounds=None, prev_displayed=None, post_smoothing=0.0, out=None, out8=None):
+    """``viewer.compose_display`` in one launch (``isrDisplayFrame``): same arguments, device tensors; -> ``out`` [1,3,4h,4w] (allocated
+    if None; must not be ``prev_displayed``).  ``out8``: a [4h,4w,4] uint8 tensor that receives the RGBA copy.  ``bounds``: the two-float
+    device tensor of ``viewer.depth_bounds`` (depth view).  No fall-back: tensors the launch does not take raise."""
+    if channel not in DISPLAY_VIEWS:
+        raise ValueError("channel must be one of %s" % (tuple(DISPLAY_VIEWS),))
+    if not display_supported(gbuffer_hwc, rgb, raw):
+        raise ValueError("display_frame: fp32 device tensors gbuffer [h,w,12], rgb [1,3,4h,4w], raw None or [1,6,4h,4w] are needed")
+    h, w = gbuffer_hwc.shape[0], gbuffer_hwc.shape[1]
+    H, W = 4 * h, 4 * w
+    dev = gbuffer_hwc.device
+    keep = [rgb.contiguous(), raw.contiguous() if raw is not None else None]
+    p = _DisplayParams()
+    p.gbuffer, p.rgb, p.raw = gbuffer_hwc.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr() if raw is not None else None
+    smoothing = prev_displayed is not None and post_smoothing != 0
+    if channel == "flow" or smoothing:
+        if filled_flow is None or tuple(filled_flow.shape) != (1, 2, h, w) or not filled_flow.is_cuda or filled_flow.dtype != torch.float32:
+            raise ValueError("display_frame: the hole-filled flow [1,2,h,w] is needed (flow view, post-smoothing)")
+        keep.append(filled_flow.contiguous())
+        p.flow = keep[-1].data_ptr()
+    if smoothing:
+        if tuple(prev_displayed.shape) != (1, 3, H, W) or not prev_displayed.is_cuda or prev_displayed.dtype != torch.float32:
+            raise ValueError("display_frame: prev_displayed must be [1,3,4h,4w] fp32 on the device")
+        keep.append(prev_displayed.contiguous())
+        p.prev = keep[-1].data_ptr()
+        p.smooth_prev = float(np.float32(post_smoothing))
+        p.smooth_cur = float(np.float32(1.0 - post_smoothing))
+    if focus is not None:
+        viewport, mask = focus
+        if focus_gbuffer is None or tuple(focus_gbuffer.shape) != (H, W, 12) or not focus_gbuffer.is_cuda or not focus_gbuffer.is_contiguous() \
+                or focus_gbuffer.dtype != torch.float32 or shading is None:
+            raise ValueError("display_frame: focus needs the full-resolution G-buffer [4h,4w,12] on the device and the shading")
+        if mask.numel() != H * W or not mask.is_cuda or mask.dtype != torch.float32:
+            raise ValueError("display_frame: the focus mask must be [1,4h,4w] fp32 on the device")
+        keep.append(mask.contiguous())
+        p.focus, p.focus_mask = focus_gbuffer.data_ptr(), keep[-1].data_ptr()
+        x0, y0, x1, y1 = (int(v) for v in viewport)
+        p.viewport = (ctypes.c_int * 4)(max(0, x0), max(0, y0), min(W, x1), min(H, y1))
+        p.shading = (ctypes.c_float * 18)(*shading.packed_parameters())
+        p.exponent, p.ao_strength, p.enable_specular = int(shading._specular_exponent), float(shading._ao), int(bool(shading.enable_specular))
+    if channel == "depth":
+        if bounds is None:
+            d = gbuffer_hwc[..., 7]
+            bounds = torch.stack([(d + (d <= 1e-5).to(d.dtype)).min(), d.max()])
+        if bounds.numel() != 2 or not bounds.is_cuda or bounds.dtype != torch.float32:
+            raise ValueError("display_frame: bounds must be two fp32 values on the device")
+        keep.append(bounds.contiguous())
+        p.depth_bounds = keep[-1].data_ptr()
+    if out is None:
+        out = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (1, 3, H, W) or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("display_frame: out must be a contiguous [1,3,4h,4w] fp32 device tensor")
+    if smoothing and out.data_ptr() == p.prev:
+        raise ValueError("display_frame: out must not be prev_displayed (the warp reads neighbouring pixels)")
+    p.out = out.data_ptr()
+    if out8 is not None:
+        if tuple(out8.shape) != (H, W, 4) or not out8.is_cuda or not out8.is_contiguous() or out8.dtype != torch.uint8:
+            raise ValueError("display_frame: out8 must be a contiguous [4h,4w,4] uint8 device tensor")
+        p.out8 = out8.data_ptr()
+    p.h, p.w, p.channel, p.masking, p.background0 = h, w, DISPLAY_VIEWS[channel], int(bool(masking)), float(background0)
+    rc = _sr().isrDisplayFrame(ctypes.byref(p), _stream())
+    if rc != 0:
+        raise RuntimeError("isrDisplayFrame failed (%d)" % rc)
     return out
