@@ -31,14 +31,6 @@
 #include "sr_profile.h"
 #include "sr_act.h"
 
-// Launch with start/stop events on the dispatch packet when profiling, as a plain launch otherwise (plain launches can be
-// captured into a HIP graph -- train.GraphedTrainStep -- the Ext form cannot be relied upon there).
-#define ISR_LAUNCH(KERNEL, GRID, BLOCK, LDS, STREAM, E0, E1, ...)                                              \
-    do {                                                                                                        \
-        if ((E0) || (E1)) hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, E0, E1, 0, __VA_ARGS__);    \
-        else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                                \
-    } while (0)
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -757,6 +749,7 @@ constexpr size_t conv_fwd_lds_bytes() { return (size_t)(2 * CHUNK + 2 * 9 * CK *
 // (45 % slower), one dwordx3 load per patch row (dword-aligned multi-dword buffer loads return the first dword in
 // every component on this part), a second accumulator (no change: the chain is not what the wave waits for).
 constexpr int ROW_VARIANT = 12;
+constexpr int SMALL_COUT_VARIANT = 6;      // conv3x3_small_cout_kernel (further down)
 
 __global__ __launch_bounds__(NTHREADS) void conv3x3_rowsplit_kernel(const ConvParams p)
 {
@@ -1680,7 +1673,7 @@ constexpr int WGRAD_MAX_SLABS = 512;
 }  // namespace
 
 // ---- optional per-dispatch timing (bench.py): start/stop events ride on the dispatch packet itself
-// (hipExtLaunchKernelGGL), so no extra barrier packets or cache flushes perturb the stream.
+// (isr_launch, sr_profile.h), so no extra barrier packets or cache flushes perturb the stream.
 struct ProfileRecord { int variant; double flops; hipEvent_t e0, e1; };
 static bool g_profile = false;
 static bool g_profile_small = false;      // isrProfileEnable(2): also the frame's small kernels (variants >= ISR_VARIANT_TRUNK_PACK)
@@ -1811,23 +1804,16 @@ int isrConv3x3ForwardStrided(const float* x, const float* wprep, const float* bi
         if (Cout > 4096) return -1;
         p.bias = zero_bias;
     }
-    static bool attr_done = false;
-    if (!attr_done) {   // > 64 KiB of dynamic LDS needs an explicit opt-in
-        (void)hipFuncSetAttribute((const void*)conv3x3_fwd_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_fwd_lds_bytes<1>());
-        (void)hipFuncSetAttribute((const void*)conv3x3_fwd_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_fwd_lds_bytes<1>());
-        (void)hipFuncSetAttribute((const void*)conv3x3_fwd_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_fwd_lds_bytes<2>());
-        (void)hipFuncSetAttribute((const void*)conv3x3_fwd_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_fwd_lds_bytes<2>());
-        attr_done = true;
-    }
+    // > 64 KiB of dynamic LDS needs an explicit opt-in
+    isr_lds_opt_in<conv3x3_fwd_kernel<1, true>, conv3x3_fwd_kernel<1, false>>((int)conv_fwd_lds_bytes<1>());
+    isr_lds_opt_in<conv3x3_fwd_kernel<2, true>, conv3x3_fwd_kernel<2, false>>((int)conv_fwd_lds_bytes<2>());
+    using FwdKernel = void (*)(ConvParams);
+    const int ups = upsample2x ? 1 : 0;        // what an upsampling variant's id is ahead of the plain one's
+    const int which = upsample2x ? 0 : 1;      // index into the kernel tables (upsampling first: the order the instantiations have in the code object)
     p.cgroups = 1;
     if (g_conv_algo == 1) {
         // two workgroups per CU, one 32-channel group each; the grid covers all groups of all tiles
-        static bool attr2_done = false;
-        if (!attr2_done) {
-            (void)hipFuncSetAttribute((const void*)conv3x3_fwd2_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_fwd2_lds_bytes<4>());
-            (void)hipFuncSetAttribute((const void*)conv3x3_fwd2_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_fwd2_lds_bytes<4>());
-            attr2_done = true;
-        }
+        isr_lds_opt_in<conv3x3_fwd2_kernel<true, 4>, conv3x3_fwd2_kernel<false, 4>>((int)conv_fwd2_lds_bytes<4>());
         p.co0 = 0;
         p.cgroups = p.coutPad / 32;
         if (nwg * p.cgroups > 0x7fffffffLL) return -1;
@@ -1838,57 +1824,31 @@ int isrConv3x3ForwardStrided(const float* x, const float* wprep, const float* bi
         const long long nwgRow = (long long)N * H * p.tilesX * p.cgroups;
         const bool rows = !upsample2x && nwgRow <= 0x7fffffffLL &&
                           ((g_conv_tile == 3) || (g_conv_tile == 0 && small && nwgSmall <= g_row_threshold));
+        static const FwdKernel tile4[2] = { conv3x3_fwd2_kernel<true, 1>, conv3x3_fwd2_kernel<false, 1> };
+        static const FwdKernel tile16[2] = { conv3x3_fwd2_kernel<true, 4>, conv3x3_fwd2_kernel<false, 4> };
+        FwdKernel kernel = tile16[which];
+        int variant = 8 + ups;
+        long long groups = nwg * p.cgroups;
+        size_t lds = conv_fwd2_lds_bytes<4>();
         if (rows) {
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (g_profile) {
-                e0 = pool_event(); e1 = pool_event();
-                g_records.push_back({ ROW_VARIANT, 2.0 * 9 * Cin * Cout * (double)N * H * W, e0, e1 });
-            }
-            ISR_LAUNCH(conv3x3_rowsplit_kernel, dim3((unsigned)nwgRow), block, 0, s, e0, e1, p);
-            return hipGetLastError() == hipSuccess ? 0 : -2;
-        }
-        if (small) {
+            kernel = conv3x3_rowsplit_kernel; variant = ROW_VARIANT; groups = nwgRow; lds = 0;
+        } else if (small) {
             p.tilesY = (int)tilesY4;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (g_profile) {
-                e0 = pool_event(); e1 = pool_event();
-                g_records.push_back({ 10 + (upsample2x ? 1 : 0), 2.0 * 9 * Cin * Cout * (double)N * H * W, e0, e1 });
-            }
-            const dim3 grid1((unsigned)nwgSmall);
-            if (upsample2x) ISR_LAUNCH((conv3x3_fwd2_kernel<true, 1>), grid1, block, conv_fwd2_lds_bytes<1>(), s, e0, e1, p);
-            else ISR_LAUNCH((conv3x3_fwd2_kernel<false, 1>), grid1, block, conv_fwd2_lds_bytes<1>(), s, e0, e1, p);
-            return hipGetLastError() == hipSuccess ? 0 : -2;
+            kernel = tile4[which]; variant = 10 + ups; groups = nwgSmall; lds = conv_fwd2_lds_bytes<1>();
         }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (g_profile) {
-            e0 = pool_event(); e1 = pool_event();
-            g_records.push_back({ 8 + (upsample2x ? 1 : 0), 2.0 * 9 * Cin * Cout * (double)N * H * W, e0, e1 });
-        }
-        const dim3 grid2((unsigned)(nwg * p.cgroups));
-        if (upsample2x) ISR_LAUNCH((conv3x3_fwd2_kernel<true, 4>), grid2, block, conv_fwd2_lds_bytes<4>(), s, e0, e1, p);
-        else ISR_LAUNCH((conv3x3_fwd2_kernel<false, 4>), grid2, block, conv_fwd2_lds_bytes<4>(), s, e0, e1, p);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        return isr_launch(variant, 2.0 * 9 * Cin * Cout * (double)N * H * W, kernel, dim3((unsigned)groups), block, lds, s, p);
     }
     // one launch per group of up to 64 output channels (2 M tiles per wave)
+    static const FwdKernel whole[2][2] = { { conv3x3_fwd_kernel<1, true>, conv3x3_fwd_kernel<1, false> }, { conv3x3_fwd_kernel<2, true>, conv3x3_fwd_kernel<2, false> } };
     for (int co0 = 0; co0 < p.coutPad; co0 += 64) {
         p.co0 = co0;
         const int mt = (p.coutPad - co0 == 32) ? 1 : 2;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (g_profile) {
-            e0 = pool_event(); e1 = pool_event();
-            const int cg = Cout - co0 < 64 ? Cout - co0 : 64;
-            g_records.push_back({ mt * 2 + (upsample2x ? 1 : 0), 2.0 * 9 * Cin * cg * (double)N * H * W, e0, e1 });
-        }
-        const size_t lds = mt == 1 ? conv_fwd_lds_bytes<1>() : conv_fwd_lds_bytes<2>();
-        if (mt == 1) {
-            if (upsample2x) ISR_LAUNCH((conv3x3_fwd_kernel<1, true>), grid, block, lds, s, e0, e1, p);
-            else ISR_LAUNCH((conv3x3_fwd_kernel<1, false>), grid, block, lds, s, e0, e1, p);
-        } else {
-            if (upsample2x) ISR_LAUNCH((conv3x3_fwd_kernel<2, true>), grid, block, lds, s, e0, e1, p);
-            else ISR_LAUNCH((conv3x3_fwd_kernel<2, false>), grid, block, lds, s, e0, e1, p);
-        }
+        const int cg = Cout - co0 < 64 ? Cout - co0 : 64;
+        const int rc = isr_launch(mt * 2 + ups, 2.0 * 9 * Cin * cg * (double)N * H * W, whole[mt - 1][which], grid, block,
+                                  mt == 1 ? conv_fwd_lds_bytes<1>() : conv_fwd_lds_bytes<2>(), s, p);
+        if (rc) return rc;
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return 0;
 }
 
 int isrActBackward(const float* gy, const float* y, float* gz, long long count, int act, float slope, void* stream)
@@ -2024,12 +1984,8 @@ int isrConv3x3WeightGradSegmentsSplitMax(const float* const* xs, const float* co
     if (nt > 0x7fffffffLL) return -1;
     p.ntiles = (int)nt;
     if ((long long)(Cin < 64 ? Cin : 64) * H * W * 4 > 0x7fffffffLL || (long long)(Cout < 64 ? Cout : 64) * H * W * 4 > 0x7fffffffLL) return -1;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_split2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS_BYTES);
-        attr_done = true;
-    }
+    isr_lds_opt_in<conv3x3_wgrad_split_kernel>(WS_LDS_BYTES);
+    isr_lds_opt_in<conv3x3_wgrad_split2_kernel>(W2_LDS_BYTES);
     const long long quads = ap.count >> 2;
     const int AB = (int)(quads < 512LL * 256 ? (quads + 255) / 256 > 0 ? (quads + 255) / 256 : 1 : 512);
     if (gzmax) {
@@ -2051,15 +2007,9 @@ int isrConv3x3WeightGradSegmentsSplitMax(const float* const* xs, const float* co
             p.co0 = co0; p.ci0 = ci0;
             p.bslabs = (db && ci0 == 0) ? bslabs : nullptr;
             // (dispatch-packet events when profiling is on, like the forward kernels: the training bench line's weight-gradient family)
-            hipEvent_t pe0 = nullptr, pe1 = nullptr;
-            isr_profile_record(ISR_VARIANT_WGRAD_SPLIT, 2.0 * 9 * (Cin - ci0 < 64 ? Cin - ci0 : 64) * (Cout - co0 < 64 ? Cout - co0 : 64) * (double)segments * N * H * W, &pe0, &pe1);
-            if (g_wgrad_split_form == 2) {
-                if (pe0 || pe1) hipExtLaunchKernelGGL(conv3x3_wgrad_split2_kernel, dim3(G), dim3(W2_THREADS), W2_LDS_BYTES, s, pe0, pe1, 0, p);
-                else hipLaunchKernelGGL(conv3x3_wgrad_split2_kernel, dim3(G), dim3(W2_THREADS), W2_LDS_BYTES, s, p);
-            } else {
-                if (pe0 || pe1) hipExtLaunchKernelGGL(conv3x3_wgrad_split_kernel, dim3(G), dim3(NTHREADS), WS_LDS_BYTES, s, pe0, pe1, 0, p);
-                else hipLaunchKernelGGL(conv3x3_wgrad_split_kernel, dim3(G), dim3(NTHREADS), WS_LDS_BYTES, s, p);
-            }
+            const double flops = 2.0 * 9 * (Cin - ci0 < 64 ? Cin - ci0 : 64) * (Cout - co0 < 64 ? Cout - co0 : 64) * (double)segments * N * H * W;
+            if (g_wgrad_split_form == 2) (void)isr_launch(ISR_VARIANT_WGRAD_SPLIT, flops, conv3x3_wgrad_split2_kernel, dim3(G), dim3(W2_THREADS), W2_LDS_BYTES, s, p);
+            else (void)isr_launch(ISR_VARIANT_WGRAD_SPLIT, flops, conv3x3_wgrad_split_kernel, dim3(G), dim3(NTHREADS), WS_LDS_BYTES, s, p);
             hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(9 * 64 + 1), dim3(256), 0, s,
                                p.slabs, G, dw, Cout, Cin, co0, ci0, (const float*)p.bslabs, db, (const float*)scale, accumulate);
         }
@@ -2318,13 +2268,7 @@ int isrConv3x3SmallCoutStrided(const float* x, const float* w8, const float* bia
     p.finish = 0;
     const long long nwg = (long long)N * p.tilesX * p.tilesY;
     if (nwg > 0x7fffffffLL) return -1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_profile) {
-        e0 = pool_event(); e1 = pool_event();
-        g_records.push_back({ 6, 2.0 * 9 * Cin * Cout * (double)N * H * W, e0, e1 });
-    }
-    ISR_LAUNCH(conv3x3_small_cout_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(SMALL_COUT_VARIANT, 2.0 * 9 * Cin * Cout * (double)N * H * W, conv3x3_small_cout_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 int isrConvSmallFinishFrame(const float* x, const float* w8, const float* bias8, const float* net_input, float* next_prev, float* rgb,
@@ -2342,13 +2286,7 @@ int isrConvSmallFinishFrame(const float* x, const float* w8, const float* bias8,
     p.xPlane = xPlane; p.xImage = (long long)Cin * xPlane;
     p.finish = 1;
     isr_fill_finish_params(p.fin, nullptr, net_input, next_prev, rgb, h, w, shading24, exponent, ao_strength, inverse_ao, enable_specular);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_profile) {
-        e0 = pool_event(); e1 = pool_event();
-        g_records.push_back({ 6, 2.0 * 9 * Cin * 6 * (double)H * W, e0, e1 });
-    }
-    ISR_LAUNCH(conv3x3_small_cout_kernel<false>, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(SMALL_COUT_VARIANT, 2.0 * 9 * Cin * 6 * (double)H * W, conv3x3_small_cout_kernel<false>, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 int isrConvSmallFinishFrameColour(const float* x, const float* w8, const float* bias8, const float* net_input, float* out3,
@@ -2365,13 +2303,7 @@ int isrConvSmallFinishFrameColour(const float* x, const float* w8, const float* 
     p.xPlane = xPlane; p.xImage = (long long)Cin * xPlane;
     p.finish = 1;
     isr_fill_finish_params(p.fin, nullptr, net_input, out3, nullptr, h, w, nullptr, 1, 0.f, 0, 0);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_profile) {
-        e0 = pool_event(); e1 = pool_event();
-        g_records.push_back({ 6, 2.0 * 9 * Cin * 3 * (double)H * W, e0, e1 });
-    }
-    ISR_LAUNCH(conv3x3_small_cout_kernel<true>, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(256), 0, (hipStream_t)stream, e0, e1, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(SMALL_COUT_VARIANT, 2.0 * 9 * Cin * 3 * (double)H * W, conv3x3_small_cout_kernel<true>, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 }  // extern "C"

@@ -309,18 +309,7 @@ void isrDebugSetBlockAblation(int bits) { g_block_dbg = bits; }
 int isrDebugBlockState(void) { return (g_block_stamps ? 1 : 0) | (g_block_dbg ? 2 : 0); }
 #endif
 
-static int block_slots()
-{
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        slots = 2 * cus;
-        (void)hipFuncSetAttribute((const void*)resblock_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_BYTES);
-    }
-    return slots;
-}
+static int block_slots() { return 2 * isr_cu_count(); }
 
 long long isrResBlockSplitWorkspaceBytes(void) { return (long long)block_slots() * SCR_UNITS * 16; }
 
@@ -349,12 +338,9 @@ int isrResBlockSplit(const float* x, const void* wq1, const float* bias1, const 
     const int slots = block_slots();
     const long long ntiles = (long long)p.tilesX * p.tilesY;
     const long long want = ntiles < slots ? ((ntiles + 7) / 8) * 8 : slots;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    isr_profile_record(ISR_VARIANT_SPLIT_BLOCK, 2.0 * 2.0 * 9 * 64 * 64 * (double)H * W, &e0, &e1);
-    hipStream_t s = (hipStream_t)stream;
-    if (e0 || e1) hipExtLaunchKernelGGL(resblock_split_kernel, dim3((unsigned)want), dim3(B_THREADS), B_LDS_BYTES, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(resblock_split_kernel, dim3((unsigned)want), dim3(B_THREADS), B_LDS_BYTES, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    isr_lds_opt_in<resblock_split_kernel>(B_LDS_BYTES);
+    return isr_launch(ISR_VARIANT_SPLIT_BLOCK, 2.0 * 2.0 * 9 * 64 * 64 * (double)H * W, resblock_split_kernel, dim3((unsigned)want), dim3(B_THREADS), B_LDS_BYTES,
+                      (hipStream_t)stream, p);
 }
 
 } // extern "C"

@@ -25,6 +25,7 @@
 
 #include "../../include/isr_sr_kernels.h"
 #include "sr_finish.h"
+#include "sr_profile.h"
 
 namespace {
 
@@ -475,14 +476,8 @@ static int forward_lp(const float* x, const void* wq, const float* bias, const f
     p.quads = ((W & 3) == 0 && aligned) ? 1 : 0;
     const long long nwg = (long long)N * p.tilesX * p.tilesY * p.cgroups;
     if (nwg > 0x7fffffffLL) return -1;
-    static bool attr_done = false;
-    if (!attr_done) {   // > 64 KiB of LDS needs an explicit opt-in
-        (void)hipFuncSetAttribute((const void*)conv3x3_f16_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_f16_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_f16_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_f16_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_BYTES);
-        attr_done = true;
-    }
+    // > 64 KiB of LDS needs an explicit opt-in
+    isr_lds_opt_in<conv3x3_f16_kernel<false, false>, conv3x3_f16_kernel<true, false>, conv3x3_f16_kernel<false, true>, conv3x3_f16_kernel<true, true>>(B_LDS_BYTES);
     const dim3 grid((unsigned)nwg), block(B_THREADS);
     hipStream_t s = (hipStream_t)stream;
     if (upsample2x) {

@@ -1144,8 +1144,6 @@ static unsigned* g_range_flag = nullptr;
 static unsigned* g_max_slots = nullptr;   // isrSetMaxSlots: per-wave maxima of the NEXT isrConv3x3ForwardSplit launch
 static int g_max_slot_cap = 0, g_max_slot_used = 0;
 unsigned* isr_take_range_flag() { unsigned* f = g_range_flag; g_range_flag = nullptr; return f; }
-static bool g_ps_in = false;       // set around the launch by isrConv3x3ForwardSplitFromPacked
-static bool g_ps_out = false;      // set around the launch by isrConv3x3ForwardSplitPacked (the library is single threaded by contract)
 [[maybe_unused]] static unsigned long long* g_split_stamps = nullptr;
 [[maybe_unused]] static int g_split_dbg = 0;
 static int g_split_small = 1;     // 2-row-tile kernel for small images (isrDebugSetSplitSmall)
@@ -1194,32 +1192,47 @@ int isrConvSplitPrepare(const float* w, void* wq, int Cout, int Cin, void* strea
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int isrConv3x3ForwardSplit(const float* x, const void* wq, const float* bias, const float* residual, float* y,
-                           int N, int Cin, int H, int W, int Cout, int act, float slope, int upsample2x,
-                           long long xPlane, long long xImage, long long yPlane, long long yImage,
-                           long long rPlane, long long rImage, void* stream)
+} // extern "C"
+
+// ---- isrConv3x3ForwardSplit and its packed-split siblings: validate and fill -> plan -> launch ------------------------------------
+namespace {
+
+struct SplitArgs {                  // the entry point's arguments
+    const float* x; const void* wq; const float* bias; const float* residual; float* y;
+    int N, Cin, H, W, Cout, act; float slope; int upsample2x;
+    long long xPlane, xImage, yPlane, yImage, rPlane, rImage;
+};
+struct SplitOptions {
+    bool packed_in = false;         // isrConv3x3ForwardSplitFromPacked: `x` is a packed-split tensor, xPlane its plane stride in units
+    bool packed_out = false;        // isrConv3x3ForwardSplitPacked: `y` is the packed-split tensor, yPlane its plane stride in units
+    bool force_tile_form = false;   // plain layers: the one-workgroup-per-tile kernel at every size (the only form that knows the packed-split layouts)
+};
+struct SplitSwitches { int algo, small, slots, ups_form; };       // the process-global diagnostic switches, as one launch sees them
+struct MaxSlots { unsigned* words; int cap; };                    // isrSetMaxSlots, taken by the launch
+
+// (a) validates; fills the parameter block (tilesY: the 8-row tiling) and takes the per-wave maxima array.  0, or the entry point's error code.
+int split_fill(const SplitArgs& a, const SplitOptions& o, unsigned* rangeFlag, SplitConvParams& p, MaxSlots& maxSlots)
 {
-    unsigned* const rangeFlag = isr_take_range_flag();       // taken FIRST: an early error return must not leave it armed for the next launch
-    if (!x || !wq || !y || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return -1;
-    if (act < ISR_ACT_NONE || act > ISR_ACT_GATE) return -1;
-    if (act == ISR_ACT_GATE && !residual) return -1;
-    const int Hin = upsample2x ? H / 2 : H, Win = upsample2x ? W / 2 : W;
-    if (upsample2x && ((H & 1) || (W & 1))) return -1;
-    if (xPlane < (long long)Hin * Win || yPlane < (long long)H * W || (residual && rPlane < (long long)H * W)) return -1;
-    if (xPlane * Cin * 4 > 0x7fffffffLL || yPlane * Cout * 4 > 0x7fffffffLL || (residual && rPlane * Cout * 4 > 0x7fffffffLL)) return -1;
-    const bool aligned = (xPlane & 3) == 0 && (xImage & 3) == 0 && ((uintptr_t)x & 15) == 0;
+    const int N = a.N, Cin = a.Cin, H = a.H, W = a.W, Cout = a.Cout;
+    if (!a.x || !a.wq || !a.y || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return -1;
+    if (a.act < ISR_ACT_NONE || a.act > ISR_ACT_GATE) return -1;
+    if (a.act == ISR_ACT_GATE && !a.residual) return -1;
+    const int Hin = a.upsample2x ? H / 2 : H, Win = a.upsample2x ? W / 2 : W;
+    if (a.upsample2x && ((H & 1) || (W & 1))) return -1;
+    if (a.xPlane < (long long)Hin * Win || a.yPlane < (long long)H * W || (a.residual && a.rPlane < (long long)H * W)) return -1;
+    if (a.xPlane * Cin * 4 > 0x7fffffffLL || a.yPlane * Cout * 4 > 0x7fffffffLL || (a.residual && a.rPlane * Cout * 4 > 0x7fffffffLL)) return -1;
+    const bool aligned = (a.xPlane & 3) == 0 && (a.xImage & 3) == 0 && ((uintptr_t)a.x & 15) == 0;
     // the upsampling variant stages aligned groups of four low-res pixels: isrConvF16SupportsUpsample() tells callers
-    if (upsample2x && !((Win & 3) == 0 && aligned)) return -3;
-    SplitConvParams p;
-    p.x = x; p.wq = (const u32x4*)wq; p.bias = bias; p.residual = residual; p.y = y;
+    if (a.upsample2x && !((Win & 3) == 0 && aligned)) return -3;
+    p.x = a.x; p.wq = (const u32x4*)a.wq; p.bias = a.bias; p.residual = a.residual; p.y = a.y;
     p.N = N; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
     p.Hin = Hin; p.Win = Win;
-    p.xPlane = (int)xPlane; p.yPlane = (int)yPlane; p.rPlane = (int)(residual ? rPlane : yPlane);
-    p.xImage = xImage; p.yImage = yImage; p.rImage = rImage;
+    p.xPlane = (int)a.xPlane; p.yPlane = (int)a.yPlane; p.rPlane = (int)(a.residual ? a.rPlane : a.yPlane);
+    p.xImage = a.xImage; p.yImage = a.yImage; p.rImage = a.rImage;
     p.ksteps = (Cin + 15) / 16; p.coutPad = ((Cout + 31) / 32) * 32;
     p.cgroups = (Cout + 63) / 64;
     p.tilesX = (W + ST_W - 1) / ST_W; p.tilesY = (H + ST_H - 1) / ST_H;
-    p.act = act; p.slope = slope;
+    p.act = a.act; p.slope = a.slope;
     ISR_DIAG_SET(p.stamps, g_split_stamps);
     ISR_DIAG_SET(p.dbg, g_split_dbg);
     p.quads = ((W & 3) == 0 && aligned) ? 1 : 0;
@@ -1227,72 +1240,41 @@ int isrConv3x3ForwardSplit(const float* x, const void* wq, const float* bias, co
     p.xps = nullptr; p.xpsPlane = 0; p.zero = nullptr;
     p.absmax = rangeFlag;
     p.slotmax = nullptr;
-    unsigned* const maxSlots = g_max_slots;
-    const int maxCap = g_max_slot_cap;
+    maxSlots = { g_max_slots, g_max_slot_cap };
     g_max_slots = nullptr; g_max_slot_cap = 0; g_max_slot_used = 0;
-    if (g_ps_in) {             // isrConv3x3ForwardSplitFromPacked: `x` is a packed-split tensor, xPlane its plane stride in units
+    if (o.packed_in) {
         static u32x4* zero = nullptr;
         if (!zero && hipGetSymbolAddress((void**)&zero, HIP_SYMBOL(g_split_zero_unit)) != hipSuccess) return -2;
-        if (N != 1 || upsample2x || (Cin & 7) || xPlane * 16 * 2 * (Cin / 8) > 0x7fffffffLL || ((uintptr_t)x & 15)) return -1;
-        p.xps = (const u32x4*)x; p.xpsPlane = (int)xPlane; p.zero = zero; p.x = nullptr;
+        if (N != 1 || a.upsample2x || (Cin & 7) || a.xPlane * 16 * 2 * (Cin / 8) > 0x7fffffffLL || ((uintptr_t)a.x & 15)) return -1;
+        p.xps = (const u32x4*)a.x; p.xpsPlane = (int)a.xPlane; p.zero = zero; p.x = nullptr;
     }
-    if (g_ps_out) {            // isrConv3x3ForwardSplitPacked: `y` is the packed-split tensor, yPlane its plane stride in units
-        if (N != 1 || residual || (Cout & 7) || act == ISR_ACT_GATE || yPlane * 16 * 2 * (Cout / 8) > 0x7fffffffLL) return -1;
-        p.ps = (u32x4*)y; p.psPlane = (int)yPlane; p.y = nullptr;
+    if (o.packed_out) {
+        if (N != 1 || a.residual || (Cout & 7) || a.act == ISR_ACT_GATE || a.yPlane * 16 * 2 * (Cout / 8) > 0x7fffffffLL) return -1;
+        p.ps = (u32x4*)a.y; p.psPlane = (int)a.yPlane; p.y = nullptr;
     }
-    const long long nwg = (long long)N * p.tilesX * p.tilesY * p.cgroups;
-    if (nwg > 0x7fffffffLL) return -1;
-    static bool attr_done = false;
-    if (!attr_done) {   // > 64 KiB of LDS needs an explicit opt-in
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES);
-        attr_done = true;
-    }
-    const dim3 grid((unsigned)nwg), block(S_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if ((long long)N * p.tilesX * p.tilesY * p.cgroups > 0x7fffffffLL) return -1;
+    return 0;
+}
+
+// (b) which form takes the layer, and on which grid: a pure function of the filled block, the options, the switches and the CU count
+SplitPlan split_plan(const SplitConvParams& p, bool upsample2x, const SplitOptions& o, const SplitSwitches& sw, int cus)
+{
+    const int algo = o.force_tile_form ? 0 : sw.algo, small = o.force_tile_form ? 0 : sw.small;
+    const long long nwg = (long long)p.N * p.tilesX * p.tilesY * p.cgroups;
+    const bool beyond_tiles = !upsample2x && p.quads && !p.stamps;       // a plain layer the forms beside the tile kernel can take
     // small images (a batch of training crops): 2-row tiles when the 8-row tiling would leave most CUs idle
-    const long long tiles2 = (long long)N * p.tilesX * ((H + R2_H - 1) / R2_H) * p.cgroups;
-    if (!upsample2x && p.quads && !g_split_stamps && g_split_small && nwg < 256 && tiles2 >= 64 && tiles2 <= 0x7fffffffLL) {
-        static bool attr2 = false;
-        if (!attr2) {
-            (void)hipFuncSetAttribute((const void*)conv3x3_split_rows2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, R2_LDS_BYTES);
-            attr2 = true;
-        }
-        p.tilesY = (H + R2_H - 1) / R2_H;
-        isr_profile_record(ISR_VARIANT_SPLIT_ROWS2, 2.0 * 9 * Cin * Cout * (double)N * H * W, &e0, &e1);
-        const dim3 g2((unsigned)tiles2);
-        if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_rows2_kernel, g2, block, R2_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL(conv3x3_split_rows2_kernel, g2, block, R2_LDS_BYTES, s, p);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (!upsample2x && p.quads && !g_split_stamps && g_split_algo == 2) {
+    const int tilesY2 = (p.H + R2_H - 1) / R2_H;
+    const long long tiles2 = (long long)p.N * p.tilesX * tilesY2 * p.cgroups;
+    if (beyond_tiles && small && nwg < 256 && tiles2 >= 64 && tiles2 <= 0x7fffffffLL)
+        return { SplitForm::Rows2, ISR_VARIANT_SPLIT_ROWS2, tilesY2, tiles2 };
+    if (beyond_tiles && algo == 2) {
         // wide form: one 512-thread workgroup per CU, 16 x 32 tiles, hand-pipelined fragment reads
-        static int cus = 0;
-        if (!cus) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-            (void)hipFuncSetAttribute((const void*)conv3x3_split_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES);
-        }
-        p.tilesY = (H + WT_H - 1) / WT_H;
-        const long long ntiles = (long long)N * p.tilesX * p.tilesY * p.cgroups;
-        const int cap = g_split_slots > 0 ? g_split_slots : cus;
-        const long long want = ntiles < cap ? ((ntiles + 7) / 8) * 8 : cap;
-        isr_profile_record(ISR_VARIANT_SPLIT_WIDE, 2.0 * 9 * Cin * Cout * (double)N * H * W, &e0, &e1);
-        const dim3 pgrid((unsigned)want), wblock(W_THREADS);
-        if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_wide_kernel, pgrid, wblock, W_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL(conv3x3_split_wide_kernel, pgrid, wblock, W_LDS_BYTES, s, p);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        const int tilesYw = (p.H + WT_H - 1) / WT_H;
+        const long long ntiles = (long long)p.N * p.tilesX * tilesYw * p.cgroups;
+        const int cap = sw.slots > 0 ? sw.slots : cus;
+        return { SplitForm::Wide, ISR_VARIANT_SPLIT_WIDE, tilesYw, ntiles < cap ? ((ntiles + 7) / 8) * 8 : cap };
     }
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        slots = 2 * cus;
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES);
-    }
+    const int slots = 2 * cus;
     // persistent form: two workgroups per CU walk the tile list with the next k-step's loads in flight under the MFMAs.  It pays
     // when a workgroup has SEVERAL tiles to walk; a launch that fits in one round (the 480 x 270 trunk: 510 tiles on 512 slots)
     // has nothing to stream into and runs faster on the one-workgroup-per-tile form with its 32-channel staging passes (half the
@@ -1301,80 +1283,113 @@ int isrConv3x3ForwardSplit(const float* x, const void* wq, const float* bias, co
     // (A few rounds do not pay either: the 1024 tiles of a 16 x 64 x 128 x 128 training layer take 66-95 us on the persistent form and
     // the step is 0.35 ms shorter with them on the one-workgroup-per-tile form; the 2040 tiles of a 960 x 540 layer of the tiled 4K
     // mode 124 against 129 us.  Beyond four rounds the persistent form stays.)
-    const bool one_round = nwg <= (g_split_slots > 0 ? g_split_slots : 4 * slots);
-    if (!upsample2x && p.quads && !g_split_stamps && (g_split_algo == 3 || (g_split_algo == 1 && !one_round))) {
-        const int cap = g_split_slots > 0 ? g_split_slots : slots;
-        const long long want = nwg < cap ? ((nwg + 7) / 8) * 8 : cap;
-        isr_profile_record(ISR_VARIANT_SPLIT_STREAM, 2.0 * 9 * Cin * Cout * (double)N * H * W, &e0, &e1);
-        const dim3 pgrid((unsigned)want);
-        if (maxSlots && 4 * want <= maxCap) { p.slotmax = maxSlots; g_max_slot_used = (int)(4 * want); }
-        if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_stream_kernel, pgrid, block, S_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL(conv3x3_split_stream_kernel, pgrid, block, S_LDS_BYTES, s, p);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    // algorithmic flops of the convolution (2 * 9 * Cin * Cout per output pixel), not the 3x matrix flops spent on it
-#ifdef ISR_DIAG
-    if (upsample2x && g_split_ups_form == 4 && isr_split_ups4_takes(p)) {
-        isr_profile_record(ISR_VARIANT_SPLIT_UPS4, 2.0 * 9 * Cin * Cout * (double)N * H * W, &e0, &e1);
-        return isr_launch_split_ups4(p, s, e0, e1);
-    }
-    if (upsample2x && g_split_ups_form == 5 && isr_split_ups5_takes(p)) {
-        // (recorded under the three-per-CU kernel's variant: the same layer, the same column of bench.py's kernel table)
-        isr_profile_record(ISR_VARIANT_SPLIT_UPS3, 2.0 * 9 * Cin * Cout * (double)N * H * W, &e0, &e1);
-        return isr_launch_split_ups5(p, (unsigned)nwg, s, e0, e1);
-    }
-#endif
-    const bool ups3 = upsample2x && (g_split_ups_form == 3 || g_split_ups_form == 4 || g_split_ups_form == 7 || g_split_ups_form == 8) && Cin > 0 && !(Cin & 15) && p.coutPad == 64 && Cout == 64 && p.cgroups == 1 && !p.xps;
-    isr_profile_record(ups3 ? ISR_VARIANT_SPLIT_UPS3 : upsample2x ? ISR_VARIANT_SPLIT_UPS : ISR_VARIANT_SPLIT, 2.0 * 9 * Cin * Cout * (double)N * H * W, &e0, &e1);
-#ifdef ISR_DIAG
-    if (ups3 && g_split_ups_form == 8) {
-        const int rc = isr_launch_split_upsw(p, s, e0, e1);
-        if (rc != -1) return rc;
-    }
-    if (ups3 && g_split_ups_form == 7) {
-        const int rc = isr_launch_split_ups4r(p, s, e0, e1);
-        if (rc != -1) return rc;
-    }
-#endif
-    if (ups3) {
-        const int rc = isr_launch_split_ups3(p, (unsigned)nwg, s, e0, e1);
-        if (rc != -1) return rc;
+    const bool one_round = nwg <= (sw.slots > 0 ? sw.slots : 4 * slots);
+    if (beyond_tiles && (algo == 3 || (algo == 1 && !one_round))) {
+        const int cap = sw.slots > 0 ? sw.slots : slots;
+        return { SplitForm::Stream, ISR_VARIANT_SPLIT_STREAM, p.tilesY, nwg < cap ? ((nwg + 7) / 8) * 8 : cap };
     }
     if (upsample2x) {
-        if (e0 || e1) hipExtLaunchKernelGGL((conv3x3_split_kernel<true>), grid, block, S_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL((conv3x3_split_kernel<true>), grid, block, S_LDS_BYTES, s, p);
-    } else {
-        if (maxSlots && !p.ps && 4 * nwg <= maxCap) { p.slotmax = maxSlots; g_max_slot_used = (int)(4 * nwg); }
-        if (e0 || e1) hipExtLaunchKernelGGL((conv3x3_split_kernel<false>), grid, block, S_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL((conv3x3_split_kernel<false>), grid, block, S_LDS_BYTES, s, p);
+        SplitPlan plan;
+#ifdef ISR_DIAG
+        if (sw.ups_form == 4 && isr_split_ups4_plan(p, cus, plan)) return plan;
+        if (sw.ups_form == 5 && isr_split_ups5_plan(p, cus, plan)) return plan;
+        if (sw.ups_form == 8 && isr_split_upsw_plan(p, cus, plan)) return plan;
+        if (sw.ups_form == 7 && isr_split_ups4r_plan(p, cus, plan)) return plan;
+#endif
+        if ((sw.ups_form == 3 || sw.ups_form == 4 || sw.ups_form == 7 || sw.ups_form == 8) && isr_split_ups3_plan(p, cus, plan)) return plan;
+        return { SplitForm::TileUps, ISR_VARIANT_SPLIT_UPS, p.tilesY, nwg };
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return { SplitForm::Tile, ISR_VARIANT_SPLIT, p.tilesY, nwg };
 }
 
+// (c) the planned form's launch
+int split_launch(SplitConvParams& p, const SplitPlan& plan, const MaxSlots& maxSlots, hipStream_t s)
+{
+    // algorithmic flops of the convolution (2 * 9 * Cin * Cout per output pixel), not the 3x matrix flops spent on it
+    const double flops = 2.0 * 9 * p.Cin * p.Cout * (double)p.N * p.H * p.W;
+    const dim3 grid((unsigned)plan.grid), block(S_THREADS);
+    p.tilesY = plan.tilesY;
+    // > 64 KiB of LDS needs an explicit opt-in
+    isr_lds_opt_in<conv3x3_split_kernel<false>, conv3x3_split_kernel<true>>(S_LDS_BYTES);
+    switch (plan.form) {
+    case SplitForm::Rows2:
+        isr_lds_opt_in<conv3x3_split_rows2_kernel>(R2_LDS_BYTES);
+        return isr_launch(plan.variant, flops, conv3x3_split_rows2_kernel, grid, block, R2_LDS_BYTES, s, p);
+    case SplitForm::Wide:
+        isr_lds_opt_in<conv3x3_split_wide_kernel>(W_LDS_BYTES);
+        return isr_launch(plan.variant, flops, conv3x3_split_wide_kernel, grid, dim3(W_THREADS), W_LDS_BYTES, s, p);
+    case SplitForm::Stream:
+        isr_lds_opt_in<conv3x3_split_stream_kernel>(S_LDS_BYTES);
+        if (maxSlots.words && 4 * plan.grid <= maxSlots.cap) { p.slotmax = maxSlots.words; g_max_slot_used = (int)(4 * plan.grid); }
+        return isr_launch(plan.variant, flops, conv3x3_split_stream_kernel, grid, block, S_LDS_BYTES, s, p);
+    case SplitForm::Ups3:
+        isr_lds_opt_in<conv3x3_split_ups3_kernel>(U3_LDS_BYTES);
+        return isr_launch(plan.variant, flops, conv3x3_split_ups3_kernel, grid, block, U3_LDS_BYTES, s, p);
+#ifdef ISR_DIAG
+    case SplitForm::Ups4:
+        isr_lds_opt_in<conv3x3_split_ups4_kernel>(U4_LDS_BYTES);
+        return isr_launch(plan.variant, flops, conv3x3_split_ups4_kernel, grid, dim3(U4_THREADS), U4_LDS_BYTES, s, p);
+    case SplitForm::Ups4r:
+        isr_lds_opt_in<conv3x3_split_ups4r_kernel>(U4R_LDS_BYTES);
+        return isr_launch(plan.variant, flops, conv3x3_split_ups4r_kernel, grid, block, U4R_LDS_BYTES, s, p);
+    case SplitForm::Ups5:
+        isr_lds_opt_in<conv3x3_split_ups5_kernel>(U5_LDS_BYTES);
+        return isr_launch(plan.variant, flops, conv3x3_split_ups5_kernel, grid, block, U5_LDS_BYTES, s, p);
+    case SplitForm::Upsw:
+        isr_lds_opt_in<conv3x3_split_upsw_kernel>(UW_LDS_BYTES);
+        return isr_launch(plan.variant, flops, conv3x3_split_upsw_kernel, grid, block, UW_LDS_BYTES, s, p);
+#endif
+    case SplitForm::TileUps:
+        return isr_launch(plan.variant, flops, conv3x3_split_kernel<true>, grid, block, S_LDS_BYTES, s, p);
+    case SplitForm::Tile:
+        if (maxSlots.words && !p.ps && 4 * plan.grid <= maxSlots.cap) { p.slotmax = maxSlots.words; g_max_slot_used = (int)(4 * plan.grid); }
+        return isr_launch(plan.variant, flops, conv3x3_split_kernel<false>, grid, block, S_LDS_BYTES, s, p);
+    default:
+        return -1;          // (a form of the diagnostics build planned in the product build: cannot happen)
+    }
+}
+
+int split_forward(const SplitArgs& a, const SplitOptions& o, void* stream)
+{
+    unsigned* const rangeFlag = isr_take_range_flag();       // taken FIRST: an early error return must not leave it armed for the next launch
+    SplitConvParams p;
+    MaxSlots maxSlots;
+    if (const int rc = split_fill(a, o, rangeFlag, p, maxSlots)) return rc;
+    const SplitPlan plan = split_plan(p, a.upsample2x != 0, o, { g_split_algo, g_split_small, g_split_slots, g_split_ups_form }, isr_cu_count());
+    return split_launch(p, plan, maxSlots, (hipStream_t)stream);
+}
+
+} // namespace
+
+extern "C" {
+
+int isrConv3x3ForwardSplit(const float* x, const void* wq, const float* bias, const float* residual, float* y,
+                           int N, int Cin, int H, int W, int Cout, int act, float slope, int upsample2x,
+                           long long xPlane, long long xImage, long long yPlane, long long yImage,
+                           long long rPlane, long long rImage, void* stream)
+{
+    return split_forward({ x, wq, bias, residual, y, N, Cin, H, W, Cout, act, slope, upsample2x, xPlane, xImage, yPlane, yImage, rPlane, rImage }, {}, stream);
+}
+
+// The packed-split layouts are known to the one-workgroup-per-tile kernels only (every upsampling layer's epilogue; plain layers are
+// forced onto the tile form for the launch).
 int isrConv3x3ForwardSplitPacked(const float* x, const void* wq, const float* bias, void* ps, int Cin, int H, int W, int Cout,
                                  int act, float slope, int upsample2x, long long xPlane, long long psPlane, void* stream)
 {
-    // only the forms whose epilogue knows the packed-split layout: the one-workgroup-per-tile kernels (every upsampling layer;
-    // plain layers are forced onto it for this launch)
-    const int algo = g_split_algo, small = g_split_small;
-    g_ps_out = true; g_split_algo = 0; g_split_small = 0;
-    const int rc = isrConv3x3ForwardSplit(x, wq, bias, nullptr, (float*)ps, 1, Cin, H, W, Cout, act, slope, upsample2x,
-                                          xPlane, xPlane * Cin, psPlane, 0, 0, 0, stream);
-    g_ps_out = false; g_split_algo = algo; g_split_small = small;
-    return rc;
+    SplitOptions o;
+    o.packed_out = true; o.force_tile_form = true;
+    return split_forward({ x, wq, bias, nullptr, (float*)ps, 1, Cin, H, W, Cout, act, slope, upsample2x, xPlane, xPlane * Cin, psPlane, 0, 0, 0 }, o, stream);
 }
 
+// `packed_out`: y is a packed-split tensor as well
 int isrConv3x3ForwardSplitFromPacked(const void* xps, const void* wq, const float* bias, const float* residual, void* y, int packed_out,
                                      int Cin, int H, int W, int Cout, int act, float slope, long long xpsPlane, long long yPlane, long long rPlane,
                                      void* stream)
 {
-    // the one-workgroup-per-tile kernel knows the packed-split layouts; `packed_out`: y is a packed-split tensor as well
-    const int algo = g_split_algo, small = g_split_small;
-    g_ps_in = true; g_ps_out = packed_out != 0; g_split_algo = 0; g_split_small = 0;
-    const int rc = isrConv3x3ForwardSplit((const float*)xps, wq, bias, residual, (float*)y, 1, Cin, H, W, Cout, act, slope, 0,
-                                          xpsPlane, xpsPlane * Cin, yPlane, yPlane * Cout, rPlane, rPlane * Cout, stream);
-    g_ps_in = false; g_ps_out = false; g_split_algo = algo; g_split_small = small;
-    return rc;
+    SplitOptions o;
+    o.packed_in = true; o.packed_out = packed_out != 0; o.force_tile_form = true;
+    return split_forward({ (const float*)xps, wq, bias, residual, (float*)y, 1, Cin, H, W, Cout, act, slope, 0,
+                           xpsPlane, xpsPlane * Cin, yPlane, yPlane * Cout, rPlane, rPlane * Cout }, o, stream);
 }
 
 // ---- phase-decomposed upsampling convolution (sr_conv_upsp.h): an experiment of round 5 (parity-green, slower than the default: profiles/r05_upsp_ablation.md).
@@ -1422,32 +1437,23 @@ int isrConvUpsPhase(const void* xps, const void* wq, const float* w, const float
     p.ps = (u32x4*)ps; p.psPlane = (int)psPlane;
     p.absmax = rangeFlag;
     hipStream_t s = (hipStream_t)stream;
-    static bool attr = false;
     static int ldsExtra = isr_diag_env_int("ISR_UPSP_LDS_EXTRA", 0);      // experiment: pad the allocation (one workgroup per CU)
     const int ldsBytes = UP_LDS_BYTES + ldsExtra;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)conv3x3_split_upsp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ldsBytes); attr = true; }
+    isr_lds_opt_in<conv3x3_split_upsp_kernel>(ldsBytes);
     // the one-pixel frame first (a few dozen waves), then the body: neither reads what the other writes
     UpsFrameParams fp;
     fp.xps = p.xps; fp.xpsPlane = p.xpsPlane; fp.w = w; fp.bias = bias; fp.ps = p.ps; fp.psPlane = p.psPlane;
     fp.Hin = h; fp.Win = wd; fp.H = p.H; fp.W = p.W; fp.act = act; fp.slope = slope; fp.absmax = rangeFlag;
     const int nf = 2 * p.W + 2 * (p.H - 2);
-    ISR_LAUNCH_PROFILED(ISR_VARIANT_UPS_FRAME, ups_frame_kernel, dim3((unsigned)((nf + 63) / 64), 8), dim3(64), 0, s, fp);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    isr_profile_record(ISR_VARIANT_SPLIT_UPSP, 2.0 * 9 * 64 * 64 * (double)p.H * p.W, &e0, &e1);
+    if (const int rc = isr_launch(ISR_VARIANT_UPS_FRAME, 0.0, ups_frame_kernel, dim3((unsigned)((nf + 63) / 64), 8), dim3(64), 0, s, fp)) return rc;
+    const double flops = 2.0 * 9 * 64 * 64 * (double)p.H * p.W;
     static int form = isr_diag_env_int("ISR_UPSP_FORM", 0);      // 0: the LDS-DMA form (default), 1: form Q (4 rows per wave, activations from L1; measured slower)
     const dim3 block(S_THREADS);
     if (form == 1) {
         p.tilesY = (h + UQ_TILE_H - 1) / UQ_TILE_H;
-        const dim3 qgrid((unsigned)(p.tilesX * p.tilesY));
-        const int qlds = UQ_LDS_BYTES + ldsExtra;
-        if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_upsq_kernel, qgrid, block, qlds, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL(conv3x3_split_upsq_kernel, qgrid, block, qlds, s, p);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        return isr_launch(ISR_VARIANT_SPLIT_UPSP, flops, conv3x3_split_upsq_kernel, dim3((unsigned)(p.tilesX * p.tilesY)), block, UQ_LDS_BYTES + ldsExtra, s, p);
     }
-    const dim3 grid((unsigned)(p.tilesX * p.tilesY));
-    if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_upsp_kernel, grid, block, ldsBytes, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(conv3x3_split_upsp_kernel, grid, block, ldsBytes, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(ISR_VARIANT_SPLIT_UPSP, flops, conv3x3_split_upsp_kernel, dim3((unsigned)(p.tilesX * p.tilesY)), block, ldsBytes, s, p);
 }
 
 #endif
@@ -1508,15 +1514,9 @@ int isrResBlockSmall(const float* x, const void* wa, const float* ba, const floa
     p.absmax = rangeFlag;
     p.zmax = (unsigned*)zmax; p.ymax = (unsigned*)ymax;
     ISR_DIAG_SET(p.dbg, g_split_dbg); ISR_DIAG_SET(p.stamps, g_split_stamps);
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)conv3x3_split_block2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, B2_LDS_BYTES); attr = true; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    isr_profile_record(ISR_VARIANT_SPLIT_BLOCK2, 2.0 * 2.0 * 9 * 64 * 64 * (double)N * H * W, &e0, &e1);
-    const dim3 grid((unsigned)(N * p.tilesY)), block(S_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_block2_kernel, grid, block, B2_LDS_BYTES, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(conv3x3_split_block2_kernel, grid, block, B2_LDS_BYTES, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    isr_lds_opt_in<conv3x3_split_block2_kernel>(B2_LDS_BYTES);
+    return isr_launch(ISR_VARIANT_SPLIT_BLOCK2, 2.0 * 2.0 * 9 * 64 * 64 * (double)N * H * W, conv3x3_split_block2_kernel, dim3((unsigned)(N * p.tilesY)), dim3(S_THREADS),
+                      B2_LDS_BYTES, (hipStream_t)stream, p);
 }
 
 } // extern "C"

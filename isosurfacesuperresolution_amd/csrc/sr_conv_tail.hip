@@ -891,26 +891,15 @@ static int tail_launch(int co, const void* xin, int packed, const void* wq6, con
         tp.xps = (const u32x4*)xin; tp.xpsPlane = (int)xPlane; tp.zero = zero;
         p.x = nullptr; p.xPlane = 0; p.xImage = 0;
     }
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        slots = 2 * cus;
+    const int slots = 2 * isr_cu_count();
 #ifdef ISR_DIAG
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
+    isr_lds_opt_in<conv3x3_split_tail_kernel<0, false>, conv3x3_split_tail_kernel<1, false>, conv3x3_split_tail_kernel<0, true>>(T_LDS_BYTES);
 #endif
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<2, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
+    isr_lds_opt_in<conv3x3_split_tail_kernel<2, false>, conv3x3_split_tail_kernel<2, true>, conv3x3_split_tail_kernel<2, false, 3>,
+                   conv3x3_split_tail_kernel<2, true, 3>>(T_LDS_BYTES);
 #ifdef ISR_DIAG
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_tail_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
+    isr_lds_opt_in<conv3x3_split_tail_kernel<4, false>, conv3x3_split_tail_kernel<4, true>>(T_LDS_BYTES);
 #endif
-    }
     const long long ntiles = (long long)p.tilesX * p.tilesY;
     const long long want = ntiles < slots ? ((ntiles + 7) / 8) * 8 : slots;
     hipStream_t s = (hipStream_t)stream;
@@ -924,61 +913,38 @@ static int tail_launch(int co, const void* xin, int packed, const void* wq6, con
     isr_profile_record(co == 3 ? ISR_VARIANT_SPLIT_TAIL_COLOUR : ISR_VARIANT_SPLIT_TAIL, 2.0 * 9 * 64 * (64 + co) * (double)H * W, &e0, &e1);
     tp.srec = tp.z + (size_t)(co == 3 ? TailShape<3>::GROUPS : TS_GROUPS) * tp.zPlane;
     const dim3 tgrid((unsigned)want), tblock(S_THREADS);
+    const auto tail = [&](auto kernel) { return isr_launch(kernel, tgrid, tblock, T_LDS_BYTES, s, e0, e1, tp); };
+    TailSFinishParams sfp;                  // of the S form's finishing kernels (every form but 0 and 1)
+    sfp.fin = tp.fin;
+    sfp.s = tp.z; sfp.rec = tp.srec; sfp.zPlane = tp.zPlane; sfp.tilesX = p.tilesX; sfp.bias8 = bias8;
     if (co == 3) {
         // three output channels: the S form, in the product and in the diagnostics build alike (the other forms are six-channel experiments)
-        TailSFinishParams fp;
-        fp.fin = tp.fin;
-        fp.s = tp.z; fp.rec = tp.srec; fp.zPlane = tp.zPlane; fp.tilesX = p.tilesX; fp.bias8 = bias8;
-        if (e0 || e1) {
-            if (packed) hipExtLaunchKernelGGL((conv3x3_split_tail_kernel<2, true, 3>), tgrid, tblock, T_LDS_BYTES, s, e0, e1, 0, tp);
-            else hipExtLaunchKernelGGL((conv3x3_split_tail_kernel<2, false, 3>), tgrid, tblock, T_LDS_BYTES, s, e0, e1, 0, tp);
-        } else {
-            if (packed) hipLaunchKernelGGL((conv3x3_split_tail_kernel<2, true, 3>), tgrid, tblock, T_LDS_BYTES, s, tp);
-            else hipLaunchKernelGGL((conv3x3_split_tail_kernel<2, false, 3>), tgrid, tblock, T_LDS_BYTES, s, tp);
-        }
-        ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH_COLOUR, tail_s_finish_kernel<3>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        const int rc = packed ? tail(conv3x3_split_tail_kernel<2, true, 3>) : tail(conv3x3_split_tail_kernel<2, false, 3>);
+        if (rc) return rc;
+        return isr_launch(ISR_VARIANT_TAIL_FINISH_COLOUR, 0.0, tail_s_finish_kernel<3>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, sfp);
     }
-#define TAIL_LAUNCH(FORM, PS)                                                                                                          \
-    do {                                                                                                                               \
-        if (e0 || e1) hipExtLaunchKernelGGL((conv3x3_split_tail_kernel<FORM, PS>), tgrid, tblock, T_LDS_BYTES, s, e0, e1, 0, tp);      \
-        else hipLaunchKernelGGL((conv3x3_split_tail_kernel<FORM, PS>), tgrid, tblock, T_LDS_BYTES, s, tp);                             \
-    } while (0)
 #ifdef ISR_DIAG     // the forms beside the default (0: 54 planes, 1: finishing inside the kernel, 4: vertical sums inside the kernel; all measured slower) exist in the diagnostics build only
     if (fused) {
-        TAIL_LAUNCH(1, false);
+        if (const int rc = tail(conv3x3_split_tail_kernel<1, false>)) return rc;
         const long long threads = 2LL * p.tilesY * W + (long long)H * 2 * p.tilesX;
-        ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_seam_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, tp);
-    } else if (g_tail_fused == 2 || g_tail_fused == 4) {
-        TailSFinishParams fp;
-        fp.fin = tp.fin;
-        fp.s = tp.z; fp.rec = tp.srec; fp.zPlane = tp.zPlane; fp.tilesX = p.tilesX; fp.bias8 = bias8;
-        if (g_tail_fused == 4) {
-            if (packed) TAIL_LAUNCH(4, true); else TAIL_LAUNCH(4, false);
-            ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_v_finish_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
-        } else {
-            if (packed) TAIL_LAUNCH(2, true); else TAIL_LAUNCH(2, false);
-            ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_s_finish_kernel<6>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
-        }
-    } else {
-        if (packed) TAIL_LAUNCH(0, true); else TAIL_LAUNCH(0, false);
+        return isr_launch(ISR_VARIANT_TAIL_FINISH, 0.0, tail_seam_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, tp);
+    }
+    if (g_tail_fused == 4) {
+        if (const int rc = packed ? tail(conv3x3_split_tail_kernel<4, true>) : tail(conv3x3_split_tail_kernel<4, false>)) return rc;
+        return isr_launch(ISR_VARIANT_TAIL_FINISH, 0.0, tail_v_finish_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, sfp);
+    }
+    if (g_tail_fused != 2) {
+        if (const int rc = packed ? tail(conv3x3_split_tail_kernel<0, true>) : tail(conv3x3_split_tail_kernel<0, false>)) return rc;
         TailFinishParams fp;
         fp.fin = tp.fin;
         fp.z = tp.z; fp.zPlane = tp.zPlane; fp.bias8 = bias8; fp.taps = g_tail_fused == 3 ? 3 : 9;
-        ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_combine_finish_kernel, dim3((W + 255) / 256, H), dim3(256), 0, s, fp);
+        return isr_launch(ISR_VARIANT_TAIL_FINISH, 0.0, tail_combine_finish_kernel, dim3((W + 255) / 256, H), dim3(256), 0, s, fp);
     }
 #else
-    {
-        (void)fused;
-        TailSFinishParams fp;
-        fp.fin = tp.fin;
-        fp.s = tp.z; fp.rec = tp.srec; fp.zPlane = tp.zPlane; fp.tilesX = p.tilesX; fp.bias8 = bias8;
-        if (packed) TAIL_LAUNCH(2, true); else TAIL_LAUNCH(2, false);
-        ISR_LAUNCH_PROFILED(ISR_VARIANT_TAIL_FINISH, tail_s_finish_kernel<6>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, fp);
-    }
+    (void)fused;
 #endif
-#undef TAIL_LAUNCH
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (const int rc = packed ? tail(conv3x3_split_tail_kernel<2, true>) : tail(conv3x3_split_tail_kernel<2, false>)) return rc;
+    return isr_launch(ISR_VARIANT_TAIL_FINISH, 0.0, tail_s_finish_kernel<6>, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, sfp);
 }
 
 } // extern "C"

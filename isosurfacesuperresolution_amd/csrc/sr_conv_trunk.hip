@@ -910,10 +910,7 @@ int isrDebugTrunkState(void)
 
 int isrTrunkDataflowMaxTiles(void)
 {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    return cus;
+    return isr_cu_count();
 }
 
 long long isrTrunkDataflowWorkspaceBytes(int cin0, int H, int W)
@@ -1007,56 +1004,32 @@ static int trunk_dataflow_launch(const float* x, bool prepacked, int cin0, long 
     // the progress counters start at zero every launch; the error word behind them is STICKY (the caller zero-fills the workspace
     // once, reads the word when it likes and resets it then): an error of any launch since the last look stays visible
     // (trunk_pack_input_kernel zeroes the counters; the 16-byte zero unit in front of them is never written)
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)trunk_dataflow_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, T16_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)trunk_dataflow_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, T16_LDS_BYTES);
+    isr_lds_opt_in<trunk_dataflow_kernel<false, 2>, trunk_dataflow_kernel<false, 4>, trunk_mt_kernel>(T16_LDS_BYTES);
 #ifdef ISR_DIAG                                                              // (the diagnostics instantiations exist in the diagnostics build only)
-        (void)hipFuncSetAttribute((const void*)trunk_dataflow_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, T16_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)trunk_dataflow_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, T16_LDS_BYTES);
-#endif
-        (void)hipFuncSetAttribute((const void*)trunk_mt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T16_LDS_BYTES);
-        attr = true;
-    }
-#ifdef ISR_DIAG
-    const bool diag = p.dbg != 0 || p.stamps != nullptr;
+    isr_lds_opt_in<trunk_dataflow_kernel<true, 2>, trunk_dataflow_kernel<true, 4>>(T16_LDS_BYTES);
 #endif
     const int npix = H * W;
-    if (!prepacked)
-        ISR_LAUNCH_PROFILED(ISR_VARIANT_TRUNK_PACK, trunk_pack_input_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)(lay.groups0 > 8 ? lay.groups0 : 8)), dim3(256), 0, s,
-                            x, cin0, xPlane, npix, xps, lay.groups0, (u32x4*)(ws + lay.fps), (u32x4*)(ws + lay.tps), p.done, ntiles);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (!prepacked) {
+        const int rc = isr_launch(ISR_VARIANT_TRUNK_PACK, 0.0, trunk_pack_input_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)(lay.groups0 > 8 ? lay.groups0 : 8)), dim3(256), 0, s,
+                                  x, cin0, xPlane, npix, xps, lay.groups0, (u32x4*)(ws + lay.fps), (u32x4*)(ws + lay.tps), p.done, ntiles);
+        if (rc) return rc;
+    }
     const int cus = isrTrunkDataflowMaxTiles();
     const bool mt = g_trunk_mt == 2 || ntiles > cus;
-    isr_profile_record(mt ? ISR_VARIANT_SPLIT_TRUNK_MT : ISR_VARIANT_SPLIT_TRUNK, 2.0 * 9 * 64 * ((double)cin0 + 2.0 * nblocks * 64) * (double)H * W, &e0, &e1);
-    const dim3 grid((unsigned)(((ntiles + 7) / 8) * 8)), block(T16_THREADS);
-    if (mt) {
-        // one workgroup per CU, each walking every cus-th tile (a whole number of XCD groups; never more workgroups than CUs: all must be resident)
-        const int round8 = ((ntiles + 7) / 8) * 8;
-        const dim3 mgrid((unsigned)(round8 < cus ? round8 : cus));
-        if (e0 || e1) hipExtLaunchKernelGGL(trunk_mt_kernel, mgrid, block, T16_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL(trunk_mt_kernel, mgrid, block, T16_LDS_BYTES, s, p);
-    } else if (g_trunk_rows == 4) {
-        const dim3 block4(256);
+    const int variant = mt ? ISR_VARIANT_SPLIT_TRUNK_MT : ISR_VARIANT_SPLIT_TRUNK;
+    const double flops = 2.0 * 9 * 64 * ((double)cin0 + 2.0 * nblocks * 64) * (double)H * W;
+    const int round8 = ((ntiles + 7) / 8) * 8;
+    const dim3 grid((unsigned)round8);
+    // multi-tile: one workgroup per CU, each walking every cus-th tile (a whole number of XCD groups; never more workgroups than CUs: all must be resident)
+    if (mt) return isr_launch(variant, flops, trunk_mt_kernel, dim3((unsigned)(round8 < cus ? round8 : cus)), dim3(T16_THREADS), T16_LDS_BYTES, s, p);
+    const dim3 block(g_trunk_rows == 4 ? 256 : T16_THREADS);
 #ifdef ISR_DIAG
-        if (diag) {
-            if (e0 || e1) hipExtLaunchKernelGGL((trunk_dataflow_kernel<true, 4>), grid, block4, T16_LDS_BYTES, s, e0, e1, 0, p);
-            else hipLaunchKernelGGL((trunk_dataflow_kernel<true, 4>), grid, block4, T16_LDS_BYTES, s, p);
-        } else
+    if (p.dbg != 0 || p.stamps != nullptr)
+        return g_trunk_rows == 4 ? isr_launch(variant, flops, trunk_dataflow_kernel<true, 4>, grid, block, T16_LDS_BYTES, s, p)
+                                 : isr_launch(variant, flops, trunk_dataflow_kernel<true, 2>, grid, block, T16_LDS_BYTES, s, p);
 #endif
-        if (e0 || e1) hipExtLaunchKernelGGL((trunk_dataflow_kernel<false, 4>), grid, block4, T16_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL((trunk_dataflow_kernel<false, 4>), grid, block4, T16_LDS_BYTES, s, p);
-    } else {
-#ifdef ISR_DIAG
-        if (diag) {
-            if (e0 || e1) hipExtLaunchKernelGGL((trunk_dataflow_kernel<true, 2>), grid, block, T16_LDS_BYTES, s, e0, e1, 0, p);
-            else hipLaunchKernelGGL((trunk_dataflow_kernel<true, 2>), grid, block, T16_LDS_BYTES, s, p);
-        } else
-#endif
-        if (e0 || e1) hipExtLaunchKernelGGL((trunk_dataflow_kernel<false, 2>), grid, block, T16_LDS_BYTES, s, e0, e1, 0, p);
-        else hipLaunchKernelGGL((trunk_dataflow_kernel<false, 2>), grid, block, T16_LDS_BYTES, s, p);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return g_trunk_rows == 4 ? isr_launch(variant, flops, trunk_dataflow_kernel<false, 4>, grid, block, T16_LDS_BYTES, s, p)
+                             : isr_launch(variant, flops, trunk_dataflow_kernel<false, 2>, grid, block, T16_LDS_BYTES, s, p);
 }
 
 } // extern "C"

@@ -358,17 +358,13 @@ __global__ __launch_bounds__(S_THREADS, 3) void conv3x3_split_ups3_kernel(const 
 
 } // namespace
 
-// Launch hook for isrConv3x3ForwardSplit: -1 if this form does not take the layer (it is for 64-channel layers, as both of
-// EnhanceNet's are).
-static int isr_launch_split_ups3(const SplitConvParams& p, unsigned nwg, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+// Does this form take the layer?  It is for 64-channel layers, as both of EnhanceNet's are.
+static bool isr_split_ups3_plan(const SplitConvParams& p, int, SplitPlan& plan)
 {
-    if (p.Cin <= 0 || (p.Cin & 15) || p.coutPad != 64 || p.Cout != 64 || p.cgroups != 1 || p.xps) return -1;
+    if (p.Cin <= 0 || (p.Cin & 15) || p.coutPad != 64 || p.Cout != 64 || p.cgroups != 1 || p.xps) return false;
     // the fp32 epilogue is compiled for quads only (split_epilogue<WIDE_ONLY>: the per-element path, 20 KB of compare-and-branch code
     // per value, is not in this kernel)
-    if (!p.ps && ((p.W | p.yPlane | p.rPlane) & 3)) return -1;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)conv3x3_split_ups3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, U3_LDS_BYTES); attr = true; }
-    if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_ups3_kernel, dim3(nwg), dim3(S_THREADS), U3_LDS_BYTES, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(conv3x3_split_ups3_kernel, dim3(nwg), dim3(S_THREADS), U3_LDS_BYTES, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (!p.ps && ((p.W | p.yPlane | p.rPlane) & 3)) return false;
+    plan = { SplitForm::Ups3, ISR_VARIANT_SPLIT_UPS3, p.tilesY, (long long)p.N * p.tilesX * p.tilesY };
+    return true;
 }

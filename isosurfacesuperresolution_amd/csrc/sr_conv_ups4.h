@@ -335,29 +335,14 @@ __global__ __launch_bounds__(U4_THREADS, 4) void conv3x3_split_ups4_kernel(const
 
 } // namespace
 
-// Launch hook for isrConv3x3ForwardSplit: -1 if this form does not take the layer (64 -> 64-channel layers without residual, as both
-// of EnhanceNet's upsampling layers are; the plane stride times 64 channels must fit the buffer descriptor's 32-bit range).
-static bool isr_split_ups4_takes(const SplitConvParams& p)
+// Does this form take the layer?  64 -> 64-channel layers without residual, as both of EnhanceNet's upsampling layers are; the plane
+// stride times 64 channels must fit the buffer descriptor's 32-bit range.  Two persistent workgroups per CU.
+static bool isr_split_ups4_plan(const SplitConvParams& p, int cus, SplitPlan& plan)
 {
-    return p.Cin > 0 && !(p.Cin & 15) && p.coutPad == 64 && p.Cout == 64 && p.cgroups == 1 && !p.xps && !p.residual && p.act != ISR_ACT_GATE && !p.slotmax;
-}
-
-static int isr_launch_split_ups4(const SplitConvParams& p, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
-{
-    if (!isr_split_ups4_takes(p)) return -1;
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        slots = 2 * cus;
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_ups4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, U4_LDS_BYTES);
-    }
+    if (!(p.Cin > 0 && !(p.Cin & 15) && p.coutPad == 64 && p.Cout == 64 && p.cgroups == 1 && !p.xps && !p.residual && p.act != ISR_ACT_GATE && !p.slotmax)) return false;
     const long long ntiles = (long long)p.N * p.tilesX * p.tilesY;
-    if (ntiles <= 0 || ntiles > 0x3fffffffLL) return -1;
-    const long long want = ntiles < slots ? ((ntiles + 7) / 8) * 8 : slots;
-    const dim3 grid((unsigned)want), block(U4_THREADS);
-    if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_ups4_kernel, grid, block, U4_LDS_BYTES, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(conv3x3_split_ups4_kernel, grid, block, U4_LDS_BYTES, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (ntiles <= 0 || ntiles > 0x3fffffffLL) return false;
+    const int slots = 2 * cus;
+    plan = { SplitForm::Ups4, ISR_VARIANT_SPLIT_UPS4, p.tilesY, ntiles < slots ? ((ntiles + 7) / 8) * 8 : slots };
+    return true;
 }

@@ -280,18 +280,14 @@ __global__ __launch_bounds__(S_THREADS, 2) void conv3x3_split_ups4r_kernel(const
 
 } // namespace
 
-// Launch hook for isrConv3x3ForwardSplit: -1 if this form does not take the layer (64 -> 64 channels, quads, as both of EnhanceNet's are).
-static int isr_launch_split_ups4r(const SplitConvParams& p0, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+// Does this form take the layer?  64 -> 64 channels, quads, as both of EnhanceNet's are.
+static bool isr_split_ups4r_plan(const SplitConvParams& p, int, SplitPlan& plan)
 {
-    if (p0.Cin <= 0 || (p0.Cin & 15) || p0.coutPad != 64 || p0.Cout != 64 || p0.cgroups != 1 || p0.xps) return -1;
-    if (!p0.ps && ((p0.W | p0.yPlane | p0.rPlane) & 3)) return -1;        // the fp32 epilogue is compiled for quads only
-    SplitConvParams p = p0;
-    p.tilesY = (p.H + U4R_TH - 1) / U4R_TH;
-    const long long nwg = (long long)p.N * p.tilesX * p.tilesY;
-    if (nwg > 0x7fffffffLL) return -1;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)conv3x3_split_ups4r_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, U4R_LDS_BYTES); attr = true; }
-    if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_ups4r_kernel, dim3((unsigned)nwg), dim3(S_THREADS), U4R_LDS_BYTES, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(conv3x3_split_ups4r_kernel, dim3((unsigned)nwg), dim3(S_THREADS), U4R_LDS_BYTES, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (p.Cin <= 0 || (p.Cin & 15) || p.coutPad != 64 || p.Cout != 64 || p.cgroups != 1 || p.xps) return false;
+    if (!p.ps && ((p.W | p.yPlane | p.rPlane) & 3)) return false;        // the fp32 epilogue is compiled for quads only
+    const int tilesY = (p.H + U4R_TH - 1) / U4R_TH;
+    const long long nwg = (long long)p.N * p.tilesX * tilesY;
+    if (nwg > 0x7fffffffLL) return false;
+    plan = { SplitForm::Ups4r, ISR_VARIANT_SPLIT_UPS3, tilesY, nwg };     // (recorded under the three-per-CU kernel's variant: the same layer, the same column of bench.py's kernel table)
+    return true;
 }

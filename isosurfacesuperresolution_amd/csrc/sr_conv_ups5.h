@@ -288,18 +288,11 @@ __global__ __launch_bounds__(S_THREADS, 2) void conv3x3_split_ups5_kernel(const 
 } // namespace
 
 // ISR_UPS_FORM=5 takes 64 -> 64 layers (as both of EnhanceNet's are); the fp32 epilogue is compiled for quads only, as in sr_conv_ups3.h
-static bool isr_split_ups5_takes(const SplitConvParams& p)
+static bool isr_split_ups5_plan(const SplitConvParams& p, int, SplitPlan& plan)
 {
     if (p.Cin <= 0 || (p.Cin & 15) || p.coutPad != 64 || p.Cout != 64 || p.cgroups != 1 || p.xps || p.stamps) return false;
-    return p.ps || !((p.W | p.yPlane | p.rPlane) & 3);
-}
-
-static int isr_launch_split_ups5(const SplitConvParams& p, unsigned nwg, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
-{
-    if (!isr_split_ups5_takes(p)) return -1;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)conv3x3_split_ups5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, U5_LDS_BYTES); attr = true; }
-    if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_ups5_kernel, dim3(nwg), dim3(S_THREADS), U5_LDS_BYTES, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(conv3x3_split_ups5_kernel, dim3(nwg), dim3(S_THREADS), U5_LDS_BYTES, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (!p.ps && ((p.W | p.yPlane | p.rPlane) & 3)) return false;
+    // (recorded under the three-per-CU kernel's variant: the same layer, the same column of bench.py's kernel table)
+    plan = { SplitForm::Ups5, ISR_VARIANT_SPLIT_UPS3, p.tilesY, (long long)p.N * p.tilesX * p.tilesY };
+    return true;
 }

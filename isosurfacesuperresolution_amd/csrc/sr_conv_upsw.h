@@ -481,24 +481,14 @@ __global__ __launch_bounds__(S_THREADS, 1) void conv3x3_split_upsw_kernel(const 
 
 } // namespace
 
-// Launch hook for isrConv3x3ForwardSplit: -1 if this form does not take the layer (64 -> 64 channels, quads, as both of EnhanceNet's are).
-static int isr_launch_split_upsw(const SplitConvParams& p0, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+// Does this form take the layer?  64 -> 64 channels, quads, as both of EnhanceNet's are.  One persistent workgroup per CU.
+static bool isr_split_upsw_plan(const SplitConvParams& p, int cus, SplitPlan& plan)
 {
-    if (p0.Cin <= 0 || (p0.Cin & 15) || p0.coutPad != 64 || p0.Cout != 64 || p0.cgroups != 1 || p0.xps) return -1;
-    if (!p0.ps && ((p0.W | p0.yPlane | p0.rPlane) & 3)) return -1;        // the fp32 epilogue is compiled for quads only
-    SplitConvParams p = p0;
-    p.tilesY = (p.H + UW_TH - 1) / UW_TH;
-    const long long tiles = (long long)p.N * p.tilesX * p.tilesY;
-    if (tiles > 0x7fffffffLL) return -1;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        (void)hipFuncSetAttribute((const void*)conv3x3_split_upsw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, UW_LDS_BYTES);
-    }
-    const unsigned grid = (unsigned)(tiles < cus ? tiles : cus);
-    if (e0 || e1) hipExtLaunchKernelGGL(conv3x3_split_upsw_kernel, dim3(grid), dim3(S_THREADS), UW_LDS_BYTES, s, e0, e1, 0, p);
-    else hipLaunchKernelGGL(conv3x3_split_upsw_kernel, dim3(grid), dim3(S_THREADS), UW_LDS_BYTES, s, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (p.Cin <= 0 || (p.Cin & 15) || p.coutPad != 64 || p.Cout != 64 || p.cgroups != 1 || p.xps) return false;
+    if (!p.ps && ((p.W | p.yPlane | p.rPlane) & 3)) return false;        // the fp32 epilogue is compiled for quads only
+    const int tilesY = (p.H + UW_TH - 1) / UW_TH;
+    const long long tiles = (long long)p.N * p.tilesX * tilesY;
+    if (tiles > 0x7fffffffLL) return false;
+    plan = { SplitForm::Upsw, ISR_VARIANT_SPLIT_UPS3, tilesY, tiles < cus ? tiles : cus };
+    return true;
 }

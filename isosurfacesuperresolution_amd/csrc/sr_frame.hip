@@ -699,8 +699,7 @@ int isrAssembleInputRect(const float* gbuffer_hwc12, const float* flow_filled, c
     if (prev_high && !flow_filled) return -1;
     if (init_mode < 0 || init_mode > 2) return -1;
     AssembleParams p = { gbuffer_hwc12, flow_filled, prev_high, net_input, h, w, init_mode, ao_inverted, row0, col0, col1, nullptr, 0, 0, nullptr, nullptr, nullptr, 0 };
-    ISR_LAUNCH_PROFILED(ISR_VARIANT_ASSEMBLE, assemble_input_kernel<false>, dim3((4 * (col1 - col0) + 255) / 256, row1 - row0), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(ISR_VARIANT_ASSEMBLE, 0.0, assemble_input_kernel<false>, dim3((4 * (col1 - col0) + 255) / 256, row1 - row0), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 /* isrAssembleInput straight into the dataflow trunk's workspace: the 101-channel input leaves PACKED-SPLIT (where isrTrunkDataflow's own
@@ -718,8 +717,7 @@ int isrAssembleInputPacked(const float* gbuffer_hwc12, const float* flow_filled,
     AssembleParams p = { gbuffer_hwc12, flow_filled, prev_high, net_input, h, w, init_mode, ao_inverted, 0, 0, w,
                          (u32x4*)(ws + off[0]), groups0, (long long)(((long long)h * w + 8) & ~7LL), (u32x4*)(ws + off[1]), (u32x4*)(ws + off[2]),
                          (unsigned*)(ws + 16), tiles };
-    ISR_LAUNCH_PROFILED(ISR_VARIANT_ASSEMBLE, assemble_input_kernel<true>, dim3((4 * w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(ISR_VARIANT_ASSEMBLE, 0.0, assemble_input_kernel<true>, dim3((4 * w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 int isrAssembleInputColour(const float* gbuffer_hwc12, const float* flow_filled, const float* prev_high3, float* net_input,
@@ -730,8 +728,7 @@ int isrAssembleInputColour(const float* gbuffer_hwc12, const float* flow_filled,
     if (init_mode != 0 && init_mode != 2) return -1;             // ("unshaded" constants do not exist for three channels)
     if ((prev_high3 || init_mode == 2) && !flow_filled) return -1;
     AssembleColourParams p = { gbuffer_hwc12, flow_filled, prev_high3, net_input, h, w, variant, init_mode };
-    ISR_LAUNCH_PROFILED(ISR_VARIANT_ASSEMBLE_COLOUR, assemble_input_colour_kernel, dim3((4 * w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(ISR_VARIANT_ASSEMBLE_COLOUR, 0.0, assemble_input_colour_kernel, dim3((4 * w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 int isrFinishFrameColour(const float* raw3, const float* net_input, float* out3, int h, int w, void* stream)
@@ -739,8 +736,7 @@ int isrFinishFrameColour(const float* raw3, const float* net_input, float* out3,
     if (!raw3 || !net_input || !out3 || h <= 0 || w <= 0) return -1;
     FinishParams p;
     isr_fill_finish_params(p, raw3, net_input, out3, nullptr, h, w, nullptr, 1, 0.f, 0, 0);
-    ISR_LAUNCH_PROFILED(ISR_VARIANT_FINISH_COLOUR, finish_frame_colour_kernel, dim3((4 * w + 255) / 256, 4 * h), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(ISR_VARIANT_FINISH_COLOUR, 0.0, finish_frame_colour_kernel, dim3((4 * w + 255) / 256, 4 * h), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 long long isrFlowFillWorkspace(int h, int w)
@@ -807,8 +803,7 @@ int isrFlowFillOne(const float* gbuffer_hwc12, float* flow_out, void* workspace,
     p.error = g_fill_error_word ? g_fill_error_word : p.sync + 2;
     p.timeoutTicks = g_fill_timeout_ticks;        // 50 ms of the 100 MHz clock unless a test shortened it
     ISR_DIAG_SET(p.fault, g_fill_fault);
-    ISR_LAUNCH_PROFILED(ISR_VARIANT_FLOW_FILL, flow_fill_one_kernel, dim3(p.tilesX * p.tilesY), dim3(F1_THREADS), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(ISR_VARIANT_FLOW_FILL, 0.0, flow_fill_one_kernel, dim3(p.tilesX * p.tilesY), dim3(F1_THREADS), 0, (hipStream_t)stream, p);
 }
 
 int isrFinishFrame(const float* raw, const float* net_input, float* next_prev, float* rgb, int h, int w,
@@ -817,8 +812,7 @@ int isrFinishFrame(const float* raw, const float* net_input, float* next_prev, f
     if (!raw || !net_input || !next_prev || h <= 0 || w <= 0 || (rgb && !shading24)) return -1;
     FinishParams p;
     isr_fill_finish_params(p, raw, net_input, next_prev, rgb, h, w, shading24, exponent, ao_strength, inverse_ao, enable_specular);
-    ISR_LAUNCH_PROFILED(ISR_VARIANT_FINISH, finish_frame_kernel, dim3((4 * w + 255) / 256, 4 * h), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return isr_launch(ISR_VARIANT_FINISH, 0.0, finish_frame_kernel, dim3((4 * w + 255) / 256, 4 * h), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 }  // extern "C"

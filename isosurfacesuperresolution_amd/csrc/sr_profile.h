@@ -1,6 +1,7 @@
 // Per-dispatch timing shared by the translation units of libisr_sr.so (bench.py reads it through isrProfile*):
 // while profiling is enabled, a launcher asks for a start/stop event pair that rides on its dispatch packet
-// (hipExtLaunchKernelGGL) and registers the launch's kernel variant and algorithmic flops.
+// and registers the launch's kernel variant and algorithmic flops.  Also the host-side helpers every launcher shares: the launch
+// itself, the CU count, the LDS opt-in.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,14 +37,45 @@ constexpr bool isr_variant_is_small(int v) { return (v >= ISR_VARIANT_TRUNK_PACK
 // Sets *e0 / *e1 to an event pair (and records the launch) when profiling is on, leaves them untouched otherwise.
 void isr_profile_record(int variant, double flops, hipEvent_t* e0, hipEvent_t* e1);
 
-// A launch that carries the event pair on its dispatch packet while profiling is on (kernels without template commas in their name).
-#define ISR_LAUNCH_PROFILED(variant, kernel, grid, block, lds, stream, ...)                                              \
-    do {                                                                                                                \
-        hipEvent_t pe0_ = nullptr, pe1_ = nullptr;                                                                      \
-        isr_profile_record(variant, 0.0, &pe0_, &pe1_);                                                                 \
-        if (pe0_ || pe1_) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, pe0_, pe1_, 0, __VA_ARGS__);          \
-        else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                         \
-    } while (0)
+// THE launch of this library.  While profiling is on the event pair rides on the dispatch packet (hipExtLaunchKernelGGL); otherwise
+// the launch is a plain hipLaunchKernelGGL -- the only kind a stream capture (hipGraph) can be relied on to record, so a launch
+// without events must never take the Ext path.  Returns 0, or -2 when the runtime refused the launch.
+template <typename... Params, typename... Args>
+static inline int isr_launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const Args&... args)
+{
+    if (e0 || e1) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, e0, e1, 0, static_cast<Params>(args)...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ... of a launch that registers itself as `variant` with `flops` algorithmic flops (0 for the kernels without matrix work)
+template <typename... Params, typename... Args>
+static inline int isr_launch(int variant, double flops, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    isr_profile_record(variant, flops, &e0, &e1);
+    return isr_launch(kernel, grid, block, lds, stream, e0, e1, args...);
+}
+
+// Compute units of the current device, looked up once per device ordinal; 256 (an MI355X) where the query fails.
+inline int isr_cu_count()
+{
+    constexpr int MAX_DEVICES = 64;
+    static int cus[MAX_DEVICES] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return 256;
+    if (!cus[dev] && (hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus[dev] <= 0)) cus[dev] = 256;
+    return cus[dev];
+}
+
+// "These kernels may use `bytes` of dynamic LDS" (more than 64 KiB needs the opt-in): one hipFuncSetAttribute per kernel per process,
+// at the first call of the instantiation, never one per launch.
+template <auto... Kernels>
+static inline void isr_lds_opt_in(int bytes)
+{
+    static const bool once = (((void)hipFuncSetAttribute((const void*)Kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)), ..., true);
+    (void)once;
+}
 
 // Range guard (SplitConvParams::absmax): isrSetRangeFlag(ptr) arms the NEXT launch of a split-operand kernel (any translation
 // unit) with a device word that receives the bit pattern of the largest |value| it stores; the launcher takes (and clears) it.

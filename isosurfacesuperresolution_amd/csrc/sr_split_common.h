@@ -65,6 +65,17 @@ struct SplitConvParams {
     unsigned* slotmax = nullptr;     // (default: parameter blocks filled field by field elsewhere -- sr_conv_block.hip, sr_conv_tail.hip -- leave it off)
 };
 
+// Host side (isrConv3x3ForwardSplit, sr_conv_split.hip): which kernel form a launch takes, and on which grid.  The upsampling forms
+// kept in headers of their own (sr_conv_ups*.h) each end in a predicate isr_split_ups*_plan(p, cus, plan): does the form take this
+// layer, and if so, with which tile rows and how many workgroups.
+enum class SplitForm { Tile, TileUps, Rows2, Wide, Stream, Ups3, Ups4, Ups4r, Ups5, Upsw };
+struct SplitPlan {
+    SplitForm form;
+    int variant;            // what the launch is recorded as (ISR_VARIANT_*)
+    int tilesY;             // SplitConvParams::tilesY of the form's tile height
+    long long grid;         // workgroups
+};
+
 // bit pattern of |v|: unsigned order = order of the magnitudes, inf above every finite value, NaN above inf (never lost)
 __device__ __forceinline__ unsigned isr_mag(float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; }
 __device__ __forceinline__ unsigned isr_umax(unsigned a, unsigned b) { return a > b ? a : b; }
