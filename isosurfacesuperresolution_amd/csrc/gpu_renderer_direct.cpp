@@ -714,7 +714,7 @@ bool launchFrame(float* out, hipStream_t stream)
     if (!buildParams(p, out, stream)) return false;
     const Args& a = g.args;
     const Volume& v = g.vol;
-    const int tiles_all = ((p.W + 7) >> 3) * ((p.H + 7) >> 3);
+    const int tiles_all = iso_tiles(p.W, p.H);
     const bool ordering = g.orderMode > 0 && g.variant == 0 && g.semantics != 1 && !g.statsOut && tiles_all <= ISO_ORDER_MAX_TILES;
     if (ordering) {
         if (!g.tileCost) {
@@ -738,17 +738,13 @@ bool launchFrame(float* out, hipStream_t stream)
     } else if (g.statsOut) {
         iso_launch_render_stats(p, g.variant, g.statsOut, stream);
     } else {
-        iso_launch_render(p, g.variant, stream, e0, e1, g.waveCap);
+        g.residentTarget += unsigned(iso_launch_render(p, g.variant, stream, e0, e1, g.waveCap));   // the capped waves of variant 2
         if (ordering) {
             int dev = 0, cus = 256;
             (void)hipGetDevice(&dev);
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
             iso_launch_tile_order(g.tileCost, g.tileOrder, tiles_all, g.orderMode, 4 * cus, stream);
             g.orderW = p.W; g.orderH = p.H;
-        }
-        if (g.variant == 2) {
-            const int tiles = ((p.W + 7) >> 3) * ((p.H + 7) >> 3);
-            g.residentTarget += unsigned(g.waveCap > 0 && g.waveCap < tiles ? (g.waveCap + 7) & ~7 : (tiles + 7) & ~7);
         }
     }
     if (hipGetLastError() != hipSuccess) return false;

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "iso_params.h"
+#include "iso_tile.h"
 
 namespace {
 
@@ -200,23 +201,14 @@ __device__ float ambient_occlusion(const IsoRenderParams& P, const IsoGvdbFrame&
     return ao / (float)n;
 }
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg)
-{
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 template <bool AO>
 __global__ __launch_bounds__(64) void iso_render_gvdb(const IsoRenderParams P, const IsoGvdbFrame F)
 {
-    const int tiles_x = (P.W + 7) >> 3, ntiles = tiles_x * ((P.H + 7) >> 3);
-    const int tile = xcd_remap(blockIdx.x, ntiles);
-    const int lane = threadIdx.x;
-    const int x = (tile % tiles_x) * 8 + (lane & 7);
-    const int y = (tile / tiles_x) * 8 + (lane >> 3);
-    if (x >= P.W || y >= P.H) return;
+    const TilePixel px = tile_pixel(P, xcd_remap(blockIdx.x, iso_tiles(P.W, P.H)), threadIdx.x);
+    const int x = px.i, y = px.j;
+    if (!px.in_image) return;
     float o[12] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.0f, 1.0f };   // ao, shadow: render_kernel.cu:219-220
-    if (x >= P.vp[0] && y >= P.vp[1] && x < P.vp[2] && y < P.vp[3]) {
+    if (px.inside) {
         const f3 rpos = mk(F.rpos[0], F.rpos[1], F.rpos[2]);
         const float u = ((float)x + 0.5f) / (float)P.W, w = ((float)y + 0.5f) / (float)P.H;
         const f3 camu = mk(F.camu[0], F.camu[1], F.camu[2]), camv = mk(F.camv[0], F.camv[1], F.camv[2]), cams = mk(F.cams[0], F.cams[1], F.cams[2]);
@@ -251,18 +243,14 @@ __global__ __launch_bounds__(64) void iso_render_gvdb(const IsoRenderParams P, c
             if (AO) o[10] = ambient_occlusion(P, F, sub(hit, scale(rdir, 1e-3f)), n, x, y);
         }
     }
-    float4* dst = reinterpret_cast<float4*>(P.out + ((size_t)y * P.W + x) * 12);
-    dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-    dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-    dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+    store_pixel(P, x, y, o);
 }
 
 }  // namespace
 
 void iso_launch_render_gvdb(const IsoRenderParams& p, const IsoGvdbFrame& f, void* stream, void* startEvent, void* stopEvent)
 {
-    const int tiles = ((p.W + 7) >> 3) * ((p.H + 7) >> 3);
-    const dim3 grid(tiles), block(64);
+    const dim3 grid(iso_tiles(p.W, p.H)), block(64);
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0 = (hipEvent_t)startEvent, e1 = (hipEvent_t)stopEvent;
     if (p.aoSamples > 0) hipExtLaunchKernelGGL(iso_render_gvdb<true>, grid, block, 0, st, e0, e1, 0, p, f);

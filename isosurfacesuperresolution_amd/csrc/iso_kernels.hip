@@ -13,15 +13,25 @@
 // affordable), samples are fp32.  This TU is compiled with -ffp-contract=off: the hit mask must be
 // bit-identical to the IEEE CPU restatement, so no FMA contraction is allowed here.
 //
-// Variant 0: every lane gathers its 8 corners from the brick in global memory (L2/MALL resident).
-// Variant 1: the wave cooperatively stages the brick most lanes need into LDS (ballot vote),
-//            lanes whose ray is inside that brick march out of LDS; see iso_render_lds below.
+// Six variants, one result (bit-identical); FLAT names the traversal (hits<FLAT>): 0 = the nested loops of
+// hits_hierarchy, 1 = hits_flat<1> (one sample per iteration), 3 = hits_flat<2> (two).  Secondary (AO) rays take FLAT 1
+// wherever the primary ray's FLAT is > 0 (cast_world).
+// Variant 0: iso_render_gather<AO, 3> -- every lane gathers its 8 corners from the brick in global memory (L2/MALL
+//            resident); also iso_render_gather_block (camera from device memory) and iso_render_stats (diagnostics).
+// Variant 1: iso_render_lds<AO> -- the wave cooperatively stages the brick most lanes need into LDS (ballot vote), lanes
+//            whose ray is inside that brick march out of LDS; its own resumable walk, the voxel march of FLAT 0.
+// Variant 2: iso_render_gather_slim<AO, 1> -- variant 5 in a 128-register budget, capped grid, waves pull tiles.
+// Variant 3: iso_render_gather_ldsslot<AO> -- variant 0 (FLAT 3) with the slot table in LDS, eight tiles per workgroup.
+// Variant 4: iso_render_gather<AO, 0>.
+// Variant 5: iso_render_gather<AO, 1>.
+// The brick store and the tables these kernels read are built in iso_build.hip.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <float.h>
 #include <stdint.h>
 
 #include "iso_params.h"
+#include "iso_tile.h"
 
 namespace {
 
@@ -139,40 +149,24 @@ __device__ __forceinline__ float interp_global(const IsoRenderParams& P, double 
                    voxel_value(P, cx + 1, cy + 1, cz), voxel_value(P, cx + 1, cy + 1, cz + 1), u, v, w);
 }
 
+// A sampler `interp(px, py, pz)` is the trilinear sample: the global gather here, LdsBrickSampler in variant 1.
+struct GatherSampler {
+    const IsoRenderParams& P;
+    __device__ __forceinline__ float operator()(double px, double py, double pz) const { return interp_global(P, px, py, pz); }
+};
+
 // IsoVolumeRayTracer.h:66-71 (float - double -> double -> float)
-__device__ __forceinline__ float interp_value(const IsoRenderParams& P, const Ray& r, double t)
+template <typename S>
+__device__ __forceinline__ float interp_value(const IsoRenderParams& P, const S& interp, const Ray& r, double t)
 {
     double px, py, pz;
     ray_at(r, t, px, py, pz);
-    return (float)((double)interp_global(P, px, py, pz) - P.iso);
+    return (float)((double)interp(px, py, pz) - P.iso);
 }
 
-// Per-leaf / per-node flags for the frame's isovalue (iso_march_flags, refreshed by the host whenever the isovalue or the
-// volume changes): bit 0 = the leaf / node exists, bit 1 = it exists and must be marched.
-// In a tile, P.leaf holds "leaf exists AND is owned by this tile": leaves of the halo are walked past like empty space.
-// Min/max skipping, exact: every sample the voxel DDA of a leaf can take reads voxels of [8b-1, 8b+9]^3 only (cells
-// 8b-1 .. 8b+8: a position may sit a rounding error outside the leaf's faces), and a trilinear value stays inside the
-// range of its 8 corners up to ~11 ulp of the seven float lerps.  If the isovalue lies outside [min, max] of that
-// neighbourhood by more than the pad, (value - iso) has one strict sign along the whole march, the reference's
-// `v0 * v1 <= 0` never fires, and stepping over the leaf is the same computation.  Long rays that cross the thin
-// low-density fringe or the dense core without meeting the surface were the tail the whole frame waited for.
-// The same one level up: node1Range = (min, max) over the ranges of the node's existing leaves.  If the isovalue lies
-// outside it, no leaf of the node can be marched, and since the leaf-level DDA is re-initialised per node
-// (IsoVolumeRayTracer.h:37-46) stepping over the whole node changes nothing downstream.
-__device__ __forceinline__ bool range_may_cross(const float* mm, double iso)
-{
-    const double lo = (double)mm[0], hi = (double)mm[1];
-    const double pad = 4e-6 * fmax(fabs(lo), fabs(hi));
-    return !(iso < lo - pad || iso > hi + pad);
-}
-
-__global__ __launch_bounds__(256) void iso_march_flags(const uint8_t* __restrict__ exists, const float* __restrict__ range, int n, double iso,
-                                                       uint8_t* __restrict__ flags)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) flags[i] = exists[i] ? (uint8_t)(1 | (range_may_cross(range + 2 * (size_t)i, iso) ? 2 : 0)) : (uint8_t)0;
-}
-
+// Per-leaf / per-node flags for the frame's isovalue (iso_march_flags in iso_build.hip): bit 0 = the leaf / node exists,
+// bit 1 = it exists and must be marched.  In a tile, P.leaf holds "leaf exists AND is owned by this tile": leaves of the halo
+// are walked past like empty space.
 __device__ __forceinline__ int leaf_flags(const IsoRenderParams& P, int x, int y, int z)
 {
     x -= P.org[0]; y -= P.org[1]; z -= P.org[2];
@@ -201,23 +195,23 @@ struct Trace {
     __device__ __forceinline__ void leaf(bool marched) { if (marched) ++leaves; else ++skipped; }
 };
 
-// IsoVolumeRayTracer.h:81-114
-template <typename TR>
-__device__ __forceinline__ bool hits_voxel(const IsoRenderParams& P, const Ray& ray, double& time, TR& tr)
+// IsoVolumeRayTracer.h:81-114, one loop for every sampler
+template <typename S, typename TR>
+__device__ __forceinline__ bool hits_voxel(const IsoRenderParams& P, const S& interp, const Ray& ray, double& time, TR& tr)
 {
     DDA d;
     dda_init<0>(d, ray);
     double t0 = d.t0;
-    float v0 = interp_value(P, ray, t0);
+    float v0 = interp_value(P, interp, ray, t0);
     tr.sample(1);
     do {
         double t1 = dda_next(d);
-        float v1 = interp_value(P, ray, t1);
+        float v1 = interp_value(P, interp, ray, t1);
         tr.sample(1);
         if (v0 * v1 <= 0.0f) {
             double t = 0.5 * (t0 + t1);
             for (int i = 0; i < 5; ++i) {
-                float v2 = interp_value(P, ray, t);
+                float v2 = interp_value(P, interp, ray, t);
                 if (v0 * v2 <= 0.0f) t1 = t;
                 else { t0 = t; v0 = v2; }
                 t = 0.5 * (t0 + t1);
@@ -230,11 +224,6 @@ __device__ __forceinline__ bool hits_voxel(const IsoRenderParams& P, const Ray& 
         v0 = v1;
     } while (dda_step(d));
     return false;
-}
-__device__ __forceinline__ bool hits_voxel(const IsoRenderParams& P, const Ray& ray, double& time)
-{
-    NoTrace nt;
-    return hits_voxel(P, ray, time, nt);
 }
 
 // IsoVolumeRayTracer.h:37-46 for node sizes 4096, 128, 8
@@ -260,7 +249,7 @@ __device__ bool hits_hierarchy(const IsoRenderParams& P, Ray& ray, double& time,
                             tr.leaf(march);
                             if (march) {
                                 ray.t0 = d0.t0; ray.t1 = dda_next(d0);
-                                if (hits_voxel(P, ray, time, tr)) return true;
+                                if (hits_voxel(P, GatherSampler{P}, ray, time, tr)) return true;
                             }
                         }
                     } while (dda_step(d0));
@@ -270,17 +259,12 @@ __device__ bool hits_hierarchy(const IsoRenderParams& P, Ray& ray, double& time,
     } while (dda_step(d2));
     return false;
 }
-__device__ bool hits_hierarchy(const IsoRenderParams& P, Ray& ray, double& time)
-{
-    NoTrace nt;
-    return hits_hierarchy(P, ray, time, nt);
-}
 
 // ---- the same traversal as ONE flat per-lane state machine ------------------------------------------------------------
 // hits_hierarchy() nests four loops; a wave runs them in lock step, so every round of the leaf loop lasts as long as the
 // longest voxel march any of its 64 rays does in that round while the rays whose leaf is skipped wait: the heaviest tile of
 // the bench frame costs 1.13 M cycles although its busiest ray, marched alone, costs 0.26 M (tools/lab/raymarch_lone.py).
-// Here every lane carries a state and each iteration of the single loop does at most WALK hierarchy steps and then ONE
+// Here every lane carries a state and each iteration of the single loop does at most one hierarchy step and then ONE
 // trilinear sample -- the leaf's first sample, a march sample or a bisection sample, all through the same code -- so a wave
 // lasts about as long as its busiest ray.  Same operations on the same values in the same per-ray order: bit-identical.
 // A level's DDA keeps only what changes: the per-axis step and delta are +-DIM and DIM * |1/dir| (DDA.h:79-103), recomputed
@@ -340,74 +324,6 @@ __device__ __forceinline__ bool lvl_step(Lvl& d, const Ray& r, double t1)
 
 enum { FS_STEP1 = 0, FS_NODE1 = 1, FS_LEAF = 2, FS_ENTER = 3, FS_MARCH = 4, FS_BISECT = 5, FS_MISS = 10, FS_HIT = 11 };
 
-template <int WALK, typename TR>
-__device__ __forceinline__ bool hits_flat(const IsoRenderParams& P, const Ray& ray, double& time, TR& tr)
-{
-    double T2;                       // end of the level-2 node's interval = d1.t1
-    Lvl d1;
-    {
-        DDA d2;
-        dda_init<12>(d2, ray);
-        bool found = false;
-        do {
-            if (has_node2(P, d2.vx, d2.vy, d2.vz)) { found = true; break; }
-        } while (dda_step(d2));
-        if (!found) return false;    // no other level-2 node exists: once the walk below leaves this one, the ray has missed
-        T2 = dda_next(d2);
-        lvl_init<7>(d1, ray, d2.t0);
-    }
-    Lvl d0, dv;
-    d0.t0 = d0.nx = d0.ny = d0.nz = 0.0; d0.vx = d0.vy = d0.vz = 0;
-    dv = d0;
-    double t1_0 = 0.0, t1_v = 0.0;   // ends of the current node's / leaf's interval (dda_next of the parent level)
-    double b1 = 0.0;                 // bisection: [dv.t0, b1]
-    float v0 = 0.0f;
-    int st = FS_NODE1;
-    while (st < FS_MISS) {
-#pragma unroll
-        for (int k = 0; k < WALK; ++k) {
-            if (st == FS_STEP1) st = lvl_step<7>(d1, ray, T2) ? FS_NODE1 : FS_MISS;
-            if (st == FS_NODE1) {
-                if (node1_flags(P, d1.vx, d1.vy, d1.vz) & 2) {
-                    t1_0 = lvl_next(d1, T2);
-                    lvl_init<3>(d0, ray, d1.t0);
-                    st = FS_LEAF;
-                } else st = FS_STEP1;
-            } else if (st == FS_LEAF) {
-                const int lf = leaf_flags(P, d0.vx, d0.vy, d0.vz);
-                const bool march = (lf & 2) != 0;
-                if (lf) tr.leaf(march);
-                if (march) {
-                    t1_v = lvl_next(d0, t1_0);
-                    lvl_init<0>(dv, ray, d0.t0);
-                    st = FS_ENTER;
-                } else if (!lvl_step<3>(d0, ray, t1_0)) st = FS_STEP1;
-            }
-        }
-        if (st >= FS_ENTER && st < FS_MISS) {
-            double t;
-            if (st == FS_ENTER) t = dv.t0;
-            else if (st == FS_MARCH) t = lvl_next(dv, t1_v);
-            else t = 0.5 * (dv.t0 + b1);
-            const float v = interp_value(P, ray, t);
-            tr.sample(1);
-            if (st == FS_ENTER) { v0 = v; st = FS_MARCH; }
-            else if (st == FS_MARCH) {
-                if (v0 * v <= 0.0f) { b1 = t; st = FS_BISECT; }             // the crossing lies in [dv.t0, t]
-                else {
-                    v0 = v;
-                    if (!lvl_step<0>(dv, ray, t1_v)) st = lvl_step<3>(d0, ray, t1_0) ? FS_LEAF : FS_STEP1;
-                }
-            } else {
-                if (v0 * v <= 0.0f) b1 = t;
-                else { dv.t0 = t; v0 = v; }
-                if (++st == FS_BISECT + 5) { time = 0.5 * (dv.t0 + b1); st = FS_HIT; }
-            }
-        }
-    }
-    return st == FS_HIT;
-}
-
 // Two samples of one ray with their gathers in flight together (interp_value twice: same operations, same results).
 // B is fetched only where hasB.
 struct SamplePos { int cx, cy, cz, idx, loc; float u, v, w; bool inb; };
@@ -463,13 +379,14 @@ __device__ __forceinline__ void interp_pair(const IsoRenderParams& P, const Ray&
     vB = (float)((double)fb - P.iso);
 }
 
-// hits_flat with the march two voxel steps per iteration: the DDA does not depend on the sampled values, so the sample
+// hits_flat<1> takes one sample per iteration, hits_flat<2> two; prologue, state and hierarchy walk are the same code.
+// SAMPLES == 2 is the march two voxel steps per iteration: the DDA does not depend on the sampled values, so the sample
 // after the next boundary is fetched together with the one at it (its gathers overlap); it is dropped when the first one
 // turns out to be the crossing or the leaf's last.  Same operations per ray in the same order otherwise: bit-identical.
-template <typename TR>
-__device__ __forceinline__ bool hits_flat2(const IsoRenderParams& P, const Ray& ray, double& time, TR& tr)
+template <int SAMPLES, typename TR>
+__device__ __forceinline__ bool hits_flat(const IsoRenderParams& P, const Ray& ray, double& time, TR& tr)
 {
-    double T2;
+    double T2;                       // end of the level-2 node's interval = d1.t1
     Lvl d1;
     {
         DDA d2;
@@ -478,14 +395,15 @@ __device__ __forceinline__ bool hits_flat2(const IsoRenderParams& P, const Ray& 
         do {
             if (has_node2(P, d2.vx, d2.vy, d2.vz)) { found = true; break; }
         } while (dda_step(d2));
-        if (!found) return false;
+        if (!found) return false;    // no other level-2 node exists: once the walk below leaves this one, the ray has missed
         T2 = dda_next(d2);
         lvl_init<7>(d1, ray, d2.t0);
     }
     Lvl d0, dv;
     d0.t0 = d0.nx = d0.ny = d0.nz = 0.0; d0.vx = d0.vy = d0.vz = 0;
     dv = d0;
-    double t1_0 = 0.0, t1_v = 0.0, b1 = 0.0;
+    double t1_0 = 0.0, t1_v = 0.0;   // ends of the current node's / leaf's interval (dda_next of the parent level)
+    double b1 = 0.0;                 // bisection: [dv.t0, b1]
     float v0 = 0.0f;
     int st = FS_NODE1;
     while (st < FS_MISS) {
@@ -507,42 +425,72 @@ __device__ __forceinline__ bool hits_flat2(const IsoRenderParams& P, const Ray& 
             } else if (!lvl_step<3>(d0, ray, t1_0)) st = FS_STEP1;
         }
         if (st >= FS_ENTER && st < FS_MISS) {
-            double tA, tB;
-            const double tprev = dv.t0;
-            bool hasB = true;
-            if (st == FS_ENTER) { tA = dv.t0; tB = lvl_next(dv, t1_v); }
-            else if (st == FS_MARCH) {
-                tA = lvl_next(dv, t1_v);
-                hasB = lvl_step<0>(dv, ray, t1_v);                           // taken back below if A is the crossing
-                tB = lvl_next(dv, t1_v);
-            } else { tA = 0.5 * (dv.t0 + b1); tB = tA; hasB = false; }
-            float vA, vB;
-            interp_pair(P, ray, tA, tB, hasB, vA, vB);
-            bool leafDone = false, stepAfter = false;
-            if (st >= FS_BISECT) {
+            if (SAMPLES == 1) {
+                double t;
+                if (st == FS_ENTER) t = dv.t0;
+                else if (st == FS_MARCH) t = lvl_next(dv, t1_v);
+                else t = 0.5 * (dv.t0 + b1);
+                const float v = interp_value(P, GatherSampler{P}, ray, t);
                 tr.sample(1);
-                if (v0 * vA <= 0.0f) b1 = tA;
-                else { dv.t0 = tA; v0 = vA; }
-                if (++st == FS_BISECT + 5) { time = 0.5 * (dv.t0 + b1); st = FS_HIT; }
+                if (st == FS_ENTER) { v0 = v; st = FS_MARCH; }
+                else if (st == FS_MARCH) {
+                    if (v0 * v <= 0.0f) { b1 = t; st = FS_BISECT; }             // the crossing lies in [dv.t0, t]
+                    else {
+                        v0 = v;
+                        if (!lvl_step<0>(dv, ray, t1_v)) st = lvl_step<3>(d0, ray, t1_0) ? FS_LEAF : FS_STEP1;
+                    }
+                } else {
+                    if (v0 * v <= 0.0f) b1 = t;
+                    else { dv.t0 = t; v0 = v; }
+                    if (++st == FS_BISECT + 5) { time = 0.5 * (dv.t0 + b1); st = FS_HIT; }
+                }
             } else {
-                bool checkB = true;
-                if (st == FS_ENTER) { v0 = vA; tr.sample(1); st = FS_MARCH; }
-                else {
+                double tA, tB;
+                const double tprev = dv.t0;
+                bool hasB = true;
+                if (st == FS_ENTER) { tA = dv.t0; tB = lvl_next(dv, t1_v); }
+                else if (st == FS_MARCH) {
+                    tA = lvl_next(dv, t1_v);
+                    hasB = lvl_step<0>(dv, ray, t1_v);                           // taken back below if A is the crossing
+                    tB = lvl_next(dv, t1_v);
+                } else { tA = 0.5 * (dv.t0 + b1); tB = tA; hasB = false; }
+                float vA, vB;
+                interp_pair(P, ray, tA, tB, hasB, vA, vB);
+                bool leafDone = false, stepAfter = false;
+                if (st >= FS_BISECT) {
                     tr.sample(1);
-                    if (v0 * vA <= 0.0f) { dv.t0 = tprev; b1 = tA; st = FS_BISECT; checkB = false; }
-                    else { v0 = vA; if (!hasB) { leafDone = true; checkB = false; } }
+                    if (v0 * vA <= 0.0f) b1 = tA;
+                    else { dv.t0 = tA; v0 = vA; }
+                    if (++st == FS_BISECT + 5) { time = 0.5 * (dv.t0 + b1); st = FS_HIT; }
+                } else {
+                    bool checkB = true;
+                    if (st == FS_ENTER) { v0 = vA; tr.sample(1); st = FS_MARCH; }
+                    else {
+                        tr.sample(1);
+                        if (v0 * vA <= 0.0f) { dv.t0 = tprev; b1 = tA; st = FS_BISECT; checkB = false; }
+                        else { v0 = vA; if (!hasB) { leafDone = true; checkB = false; } }
+                    }
+                    if (checkB) {
+                        tr.sample(1);
+                        if (v0 * vB <= 0.0f) { b1 = tB; st = FS_BISECT; }
+                        else { v0 = vB; stepAfter = true; }
+                    }
                 }
-                if (checkB) {
-                    tr.sample(1);
-                    if (v0 * vB <= 0.0f) { b1 = tB; st = FS_BISECT; }
-                    else { v0 = vB; stepAfter = true; }
-                }
+                if (stepAfter && !lvl_step<0>(dv, ray, t1_v)) leafDone = true;
+                if (leafDone) st = lvl_step<3>(d0, ray, t1_0) ? FS_LEAF : FS_STEP1;
             }
-            if (stepAfter && !lvl_step<0>(dv, ray, t1_v)) leafDone = true;
-            if (leafDone) st = lvl_step<3>(d0, ray, t1_0) ? FS_LEAF : FS_STEP1;
         }
     }
     return st == FS_HIT;
+}
+
+// The one place that maps FLAT to a traversal: 0 = hits_hierarchy, 1 = hits_flat<1>, 3 = hits_flat<2>
+template <int FLAT, typename TR>
+__device__ __forceinline__ bool hits(const IsoRenderParams& P, Ray& ray, double& time, TR& tr)
+{
+    if (FLAT == 3) return hits_flat<2>(P, ray, time, tr);
+    if (FLAT > 0) return hits_flat<1>(P, ray, time, tr);
+    return hits_hierarchy(P, ray, time, tr);
 }
 
 __device__ __forceinline__ double len3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
@@ -625,10 +573,8 @@ __device__ bool cast_world(const IsoRenderParams& P, double ox, double oy, doubl
 #undef ISO_SLAB
     r.t0 = t0; r.t1 = t1;
     double it;
-    bool hit;
-    if (FLAT > 0) { NoTrace nt; hit = hits_flat<1>(P, r, it, nt); }        // the secondary rays take the one-sample form (registers)
-    else hit = hits_hierarchy(P, r, it);
-    if (!hit) return false;
+    NoTrace nt;
+    if (!hits<(FLAT > 0 ? 1 : 0)>(P, r, it, nt)) return false;             // the secondary rays take the one-sample form (registers)
     double px, py, pz;
     ray_at(r, it, px, py, pz);
     hx = px * P.s + P.t[0]; hy = py * P.s + P.t[1]; hz = pz * P.s + P.t[2];
@@ -667,6 +613,19 @@ __device__ __forceinline__ double ao_value(const IsoRenderParams& P, double dist
     return yv * yv * (3.0 - (2.0 * yv));
 }
 
+// The AO sample: the ray of hemisphere sample s from origin p (normal n, frame f); true and its distance where it hits.
+// ambient_occlusion() and iso_ao_dist_kernel both cast through here: the tiled-AO proof needs one arithmetic.
+template <int FLAT>
+__device__ __forceinline__ bool ao_sample_distance(const IsoRenderParams& P, const AoFrame& f, double px, double py, double pz,
+                                                   double nx, double ny, double nz, int s, double& dist)
+{
+    double wx, wy, wz, hx, hy, hz;
+    ao_direction(P, f, nx, ny, nz, s, wx, wy, wz);
+    if (!cast_world<FLAT>(P, px, py, pz, wx, wy, wz, hx, hy, hz)) return false;
+    dist = len3(px - hx, py - hy, pz - hz);
+    return true;
+}
+
 template <int FLAT>
 __device__ double ambient_occlusion(const IsoRenderParams& P, double px, double py, double pz,
                                     double nx, double ny, double nz, int x, int y)
@@ -675,12 +634,8 @@ __device__ double ambient_occlusion(const IsoRenderParams& P, double px, double 
     double ao = 0.0;
     const int n = P.aoSamples > 512 ? 512 : P.aoSamples;
     for (int i = 0; i < n; ++i) {
-        double wx, wy, wz;
-        ao_direction(P, f, nx, ny, nz, i, wx, wy, wz);
-        double hx, hy, hz;
-        double value = 1.0;
-        if (cast_world<FLAT>(P, px, py, pz, wx, wy, wz, hx, hy, hz)) value = ao_value(P, len3(px - hx, py - hy, pz - hz));
-        ao += value;
+        double d;
+        ao += ao_sample_distance<FLAT>(P, f, px, py, pz, nx, ny, nz, i, d) ? ao_value(P, d) : 1.0;
     }
     return ao / n;
 }
@@ -750,51 +705,39 @@ __device__ __forceinline__ void shade_hit(const IsoRenderParams& P, const Ray& r
     }
 }
 
-__device__ __forceinline__ void store_pixel(const IsoRenderParams& P, int i, int j, const float o[12])
-{
-    float4* dst = reinterpret_cast<float4*>(P.out + ((size_t)j * P.W + i) * 12);
-    dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-    dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-    dst[2] = make_float4(o[8], o[9], o[10], o[11]);
-}
-
-// XCD-aware tile order: blocks b and b+8 share an XCD/L2, so give each XCD a contiguous run of
-// tiles (neighbouring pixel tiles walk the same bricks).  Bijective for any tile count.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg)
-{
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
-// ---- variant 0: per-lane gather ------------------------------------------------------------
-// FLAT: 0 = the nested loops of hits_hierarchy, 1 = hits_flat (one sample per iteration), 3 = hits_flat2 (two)
-template <bool AO, int FLAT = 3>
-__device__ __forceinline__ void render_gather_tile(const IsoRenderParams& P, int vb, int tiles_x, int ntiles, int lane, bool remap = true)
+// ---- variants 0, 2, 3, 4, 5: per-lane gather ------------------------------------------------------------
+// One pixel of one tile: workgroup / queue entry vb -> raster tile (cost order, XCD-aware scan order, or vb itself), ray,
+// traversal hits<FLAT>, shading, store.  Returns the raster tile; tr counts what the ray did, hit whether it hit (iso_render_stats).
+template <bool AO, int FLAT, typename TR>
+__device__ __forceinline__ int render_gather_tile(const IsoRenderParams& P, int vb, int lane, bool remap, TR& tr, bool& hit)
 {
     const bool ordered = remap && P.tileOrder != nullptr;
     const long long c0 = P.tileCost ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    const int tile = ordered ? (int)P.tileOrder[vb] : (remap ? xcd_remap(vb, ntiles) : vb);
-    const int i = (tile % tiles_x) * 8 + (lane & 7);
-    const int j = (tile / tiles_x) * 8 + (lane >> 3);
-    if (i >= P.W || j >= P.H) return;
+    const int tile = ordered ? (int)P.tileOrder[vb] : (remap ? xcd_remap(vb, iso_tiles(P.W, P.H)) : vb);
+    const TilePixel px = tile_pixel(P, tile, lane);
+    hit = false;
+    if (!px.in_image) return tile;
     float o[12] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.0f, 0.f };
-    const bool inside = i >= P.vp[0] && j >= P.vp[1] && i < P.vp[2] && j < P.vp[3];
-    if (inside) {
+    if (px.inside) {
         o[8] = -0.0f; o[9] = -0.0f;
         Ray r;
         double wdx, wdy, wdz, it;
-        bool hit = make_ray(P, i, j, r, wdx, wdy, wdz);
-        if (hit) {
-            if (FLAT == 3) { NoTrace nt; hit = hits_flat2(P, r, it, nt); }
-            else if (FLAT > 0) { NoTrace nt; hit = hits_flat<1>(P, r, it, nt); }
-            else hit = hits_hierarchy(P, r, it);
-        }
-        if (hit) shade_hit<AO, FLAT>(P, r, it, wdx, wdy, wdz, i, j, o);
+        hit = make_ray(P, px.i, px.j, r, wdx, wdy, wdz);
+        if (hit) hit = hits<FLAT>(P, r, it, tr);
+        if (hit) shade_hit<AO, FLAT>(P, r, it, wdx, wdy, wdz, px.i, px.j, o);
     }
-    store_pixel(P, i, j, o);
+    store_pixel(P, px.i, px.j, o);
     // the wave's cost for the next frame's dispatch order: its lanes leave the traversal together, any lane may write
     if (P.tileCost && remap && lane == 0)
         P.tileCost[tile] = (unsigned)((long long)__builtin_amdgcn_s_memtime() - c0);
+    return tile;
+}
+template <bool AO, int FLAT>
+__device__ __forceinline__ void render_gather_tile(const IsoRenderParams& P, int vb, int lane, bool remap = true)
+{
+    NoTrace nt;
+    bool hit;
+    render_gather_tile<AO, FLAT>(P, vb, lane, remap, nt, hit);
 }
 
 // ---- ray-cast AO of a tiled volume, exactly ------------------------------------------------------------------------
@@ -805,21 +748,17 @@ __device__ __forceinline__ void render_gather_tile(const IsoRenderParams& P, int
 __global__ __launch_bounds__(64) void iso_ao_dist_kernel(const IsoRenderParams P, const double* __restrict__ hitState,
                                                           const float* __restrict__ gbuf, double* __restrict__ dist)
 {
-    const int tiles_x = (P.W + 7) >> 3, ntiles = tiles_x * ((P.H + 7) >> 3);
-    const int tile = xcd_remap(blockIdx.x, ntiles), lane = threadIdx.x;
-    const int i = (tile % tiles_x) * 8 + (lane & 7), j = (tile / tiles_x) * 8 + (lane >> 3);
-    if (i >= P.W || j >= P.H) return;
-    const size_t pix = (size_t)j * P.W + i;
+    const TilePixel t = tile_pixel(P, xcd_remap(blockIdx.x, iso_tiles(P.W, P.H)), threadIdx.x);
+    if (!t.in_image) return;
+    const size_t pix = (size_t)t.j * P.W + t.i;
     if (gbuf[pix * 12 + 3] != 1.0f) return;
     const double* hs = hitState + pix * 6;
     const double px = hs[0], py = hs[1], pz = hs[2], nx = hs[3], ny = hs[4], nz = hs[5];
-    const AoFrame f = ao_frame(P, nx, ny, nz, i, j);
+    const AoFrame f = ao_frame(P, nx, ny, nz, t.i, t.j);
     const int n = P.aoSamples > 512 ? 512 : P.aoSamples;
     for (int s = 0; s < n; ++s) {
-        double wx, wy, wz, hx, hy, hz;
-        ao_direction(P, f, nx, ny, nz, s, wx, wy, wz);
-        double d = __builtin_huge_val();
-        if (cast_world<3>(P, px, py, pz, wx, wy, wz, hx, hy, hz)) d = len3(px - hx, py - hy, pz - hz);
+        double d;
+        if (!ao_sample_distance<3>(P, f, px, py, pz, nx, ny, nz, s, d)) d = __builtin_huge_val();
         dist[pix * n + s] = d;
     }
 }
@@ -869,8 +808,7 @@ __global__ __launch_bounds__(1024) void iso_tile_order_kernel(const unsigned* __
 template <bool AO, int FLAT>
 __global__ __launch_bounds__(64) void iso_render_gather(const IsoRenderParams P)
 {
-    const int tiles_x = (P.W + 7) >> 3, ntiles = tiles_x * ((P.H + 7) >> 3);
-    render_gather_tile<AO, FLAT>(P, blockIdx.x, tiles_x, ntiles, threadIdx.x);
+    render_gather_tile<AO, FLAT>(P, blockIdx.x, threadIdx.x);
 }
 
 // The same kernel with the per-frame part of the parameter block (camera, previous camera, light) read from DEVICE memory through
@@ -889,8 +827,7 @@ __global__ __launch_bounds__(64) void iso_render_gather_block(const IsoRenderPar
     for (int i = 0; i < 16; ++i) (&P.Vlast[0][0])[i] = src[NC + i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) P.light[i] = src[NC + 16 + i];
-    const int tiles_x = (P.W + 7) >> 3, ntiles = tiles_x * ((P.H + 7) >> 3);
-    render_gather_tile<false, 3>(P, blockIdx.x, tiles_x, ntiles, threadIdx.x);
+    render_gather_tile<false, 3>(P, blockIdx.x, threadIdx.x);
 }
 
 __global__ __launch_bounds__(64) void iso_write_block_kernel(const IsoFrameBlock b, IsoFrameBlock* dst)
@@ -900,31 +837,20 @@ __global__ __launch_bounds__(64) void iso_write_block_kernel(const IsoFrameBlock
     for (int i = threadIdx.x; i < (int)(sizeof(IsoFrameBlock) / 4); i += 64) d[i] = s[i];
 }
 
-// ---- diagnostics: variant 0 with per-tile clocks and per-ray step counts (never on the product path) ------------------
+// ---- diagnostics: the gather render with per-tile clocks and per-ray step counts (never on the product path) ------------
 // out[tile] = { cycles of the wave (s_memtime), samples of its busiest ray, leaves marched / skipped by that ray,
 //               sum of samples over its rays, rays that hit }
 template <int FLAT>
 __global__ __launch_bounds__(64) void iso_render_stats(const IsoRenderParams P, long long* __restrict__ out)
 {
     const long long c0 = (long long)__builtin_amdgcn_s_memtime();
-    const int tiles_x = (P.W + 7) >> 3, ntiles = tiles_x * ((P.H + 7) >> 3);
-    const int tile = xcd_remap(blockIdx.x, ntiles), lane = threadIdx.x;
-    const int i = (tile % tiles_x) * 8 + (lane & 7), j = (tile / tiles_x) * 8 + (lane >> 3);
+    const int lane = threadIdx.x;
     Trace tr;
-    int hit = 0;
-    if (i < P.W && j < P.H && i >= P.vp[0] && j >= P.vp[1] && i < P.vp[2] && j < P.vp[3]) {
-        Ray r;
-        double wdx, wdy, wdz, it;
-        float o[12] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.0f, 0.f };
-        bool h = make_ray(P, i, j, r, wdx, wdy, wdz);
-        if (h) h = FLAT == 3 ? hits_flat2(P, r, it, tr) : (FLAT > 0 ? hits_flat<1>(P, r, it, tr) : hits_hierarchy(P, r, it, tr));
-        if (h) {
-            shade_hit<false>(P, r, it, wdx, wdy, wdz, i, j, o);
-            hit = 1;
-        }
-        store_pixel(P, i, j, o);
-    }
-    int best = tr.samples, lv = tr.leaves, sk = tr.skipped, sum = tr.samples, hits = hit;
+    bool hit;
+    IsoRenderParams Q = P;
+    Q.tileCost = nullptr; Q.tileOrder = nullptr;            // never launched together with cost ordering (launchFrame)
+    const int tile = render_gather_tile<false, FLAT>(Q, blockIdx.x, lane, true, tr, hit);
+    int best = tr.samples, lv = tr.leaves, sk = tr.skipped, sum = tr.samples, hits = hit ? 1 : 0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const int ob = __shfl_xor(best, off), ol = __shfl_xor(lv, off), os = __shfl_xor(sk, off);
@@ -959,10 +885,9 @@ __global__ __launch_bounds__(512) void iso_render_gather_ldsslot(const IsoRender
     __syncthreads();
     IsoRenderParams Q = P;
     Q.slot = slotLds;
-    const int tiles_x = (P.W + 7) >> 3, ntiles = tiles_x * ((P.H + 7) >> 3);
     // the eight tiles of a workgroup are neighbours in the image, and an XCD gets a contiguous run of workgroups
     const int vb = xcd_remap(blockIdx.x, gridDim.x) * 8 + (threadIdx.x >> 6);
-    if (vb < ntiles) render_gather_tile<AO>(Q, vb, tiles_x, ntiles, threadIdx.x & 63, false);
+    if (vb < iso_tiles(P.W, P.H)) render_gather_tile<AO, 3>(Q, vb, threadIdx.x & 63, false);
 }
 
 // ---- variant 2: the same code in a 128-register budget ----------------------------------------
@@ -985,7 +910,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // steals from the next XCD's.  Every wave ends after 8 failed fetches: the grid always drains.
     if (threadIdx.x == 0) atomicAdd(P.resident, 4u);      // "this workgroup's four waves have their slots" -- see
                                                           // iso_gate_kernel; one atomic per workgroup: 1024 on one address serialise
-    const int tiles_x = (P.W + 7) >> 3, ntiles = tiles_x * ((P.H + 7) >> 3);
+    const int ntiles = iso_tiles(P.W, P.H);
     const int q = ntiles >> 3, r = ntiles & 7, xcd = blockIdx.x & 7;
     for (int s = 0; s < 8; ++s) {
         const int k = (xcd + s) & 7;
@@ -995,7 +920,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             if (lane == 0) i = atomicAdd(&P.tileQueue[k], 1u);
             i = (unsigned)__builtin_amdgcn_readfirstlane((int)i);
             if (i >= cnt) break;
-            render_gather_tile<AO, FLAT>(P, (int)i * 8 + k, tiles_x, ntiles, lane);
+            render_gather_tile<AO, FLAT>(P, (int)i * 8 + k, lane);
         }
     }
 }
@@ -1075,73 +1000,43 @@ __device__ __forceinline__ bool walk_leave_leaf(Walk& w)
     return false;
 }
 
-__device__ __forceinline__ float interp_cached(const IsoRenderParams& P, const float* __restrict__ lds, int cachedBrick,
-                                               double px, double py, double pz)
-{
-    const int cx = (int)floor(px), cy = (int)floor(py), cz = (int)floor(pz);
-    const int lx = cx - P.org[0], ly = cy - P.org[1], lz = cz - P.org[2];
-    if ((unsigned)lx < (unsigned)P.nx && (unsigned)ly < (unsigned)P.ny && (unsigned)lz < (unsigned)P.nz &&
-        ((lz >> 3) * P.nby + (ly >> 3)) * P.nbx + (lx >> 3) == cachedBrick) {
-        const float u = (float)px - (float)cx;
-        const float v = (float)py - (float)cy;
-        const float w = (float)pz - (float)cz;
-        return interp_from_brick(lds, cx & 7, cy & 7, cz & 7, u, v, w);
-    }
-    return interp_global(P, px, py, pz);
-}
-
-__device__ __forceinline__ bool hits_voxel_cached(const IsoRenderParams& P, const float* lds, int cachedBrick,
-                                                  const Ray& ray, double& time)
-{
-    auto value = [&](double t) -> float {
-        double px, py, pz;
-        ray_at(ray, t, px, py, pz);
-        return (float)((double)interp_cached(P, lds, cachedBrick, px, py, pz) - P.iso);
-    };
-    DDA d;
-    dda_init<0>(d, ray);
-    double t0 = d.t0;
-    float v0 = value(t0);
-    do {
-        double t1 = dda_next(d);
-        float v1 = value(t1);
-        if (v0 * v1 <= 0.0f) {
-            double t = 0.5 * (t0 + t1);
-            for (int i = 0; i < 5; ++i) {
-                float v2 = value(t);
-                if (v0 * v2 <= 0.0f) t1 = t;
-                else { t0 = t; v0 = v2; }
-                t = 0.5 * (t0 + t1);
-            }
-            time = t;
-            return true;
+// the staged brick where the sample's cell lies in it, the global gather otherwise (entry / exit faces)
+struct LdsBrickSampler {
+    const IsoRenderParams& P;
+    const float* __restrict__ lds;
+    int cachedBrick;
+    __device__ __forceinline__ float operator()(double px, double py, double pz) const
+    {
+        const int cx = (int)floor(px), cy = (int)floor(py), cz = (int)floor(pz);
+        const int lx = cx - P.org[0], ly = cy - P.org[1], lz = cz - P.org[2];
+        if ((unsigned)lx < (unsigned)P.nx && (unsigned)ly < (unsigned)P.ny && (unsigned)lz < (unsigned)P.nz &&
+            ((lz >> 3) * P.nby + (ly >> 3)) * P.nbx + (lx >> 3) == cachedBrick) {
+            const float u = (float)px - (float)cx;
+            const float v = (float)py - (float)cy;
+            const float w = (float)pz - (float)cz;
+            return interp_from_brick(lds, cx & 7, cy & 7, cz & 7, u, v, w);
         }
-        t0 = t1;
-        v0 = v1;
-    } while (dda_step(d));
-    return false;
-}
+        return interp_global(P, px, py, pz);
+    }
+};
 
 template <bool AO>
 __global__ __launch_bounds__(64) void iso_render_lds(const IsoRenderParams P)
 {
     __shared__ __attribute__((aligned(16))) float brickLds[ISO_BRICK_STRIDE];
-    const int tiles_x = (P.W + 7) >> 3, tiles_y = (P.H + 7) >> 3;
-    const int tile = xcd_remap(blockIdx.x, tiles_x * tiles_y);
     const int lane = threadIdx.x;
-    const int i = (tile % tiles_x) * 8 + (lane & 7);
-    const int j = (tile / tiles_x) * 8 + (lane >> 3);
-    const bool in_image = i < P.W && j < P.H;
+    const TilePixel px = tile_pixel(P, xcd_remap(blockIdx.x, iso_tiles(P.W, P.H)), lane);
+    const int i = px.i, j = px.j;
     float o[12] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.0f, 0.f };
-    const bool inside = in_image && i >= P.vp[0] && j >= P.vp[1] && i < P.vp[2] && j < P.vp[3];
     Ray r;
     Walk w;
     double wdx = 0, wdy = 0, wdz = 0, it = 0;
     int brick = -1;
     bool hit = false;
+    NoTrace nt;
     // state: 0 = walking to the next leaf, 1 = waiting at a leaf, 2 = finished
     int state = 2;
-    if (inside) {
+    if (px.inside) {
         o[8] = -0.0f; o[9] = -0.0f;
         if (make_ray(P, i, j, r, wdx, wdy, wdz)) {
             dda_init<12>(w.d2, r);
@@ -1164,222 +1059,59 @@ __global__ __launch_bounds__(64) void iso_render_lds(const IsoRenderParams P)
         }
         __syncthreads();
         if (state == 1 && brick == chosen) {
-            if (hits_voxel_cached(P, brickLds, chosen, r, it)) { hit = true; state = 2; }
+            if (hits_voxel(P, LdsBrickSampler{P, brickLds, chosen}, r, it, nt)) { hit = true; state = 2; }
             else state = walk_leave_leaf(w) ? 0 : 2;
         }
         __syncthreads();                                       // everyone done reading before the next stage
     }
     if (hit) shade_hit<AO>(P, r, it, wdx, wdy, wdz, i, j, o);
-    if (in_image) store_pixel(P, i, j, o);
-}
-
-// ---- brick builder -------------------------------------------------------------------------
-// One 64-lane workgroup per 8^3 brick position.  flag9: any non-zero among the 9^3 apron values
-// (brick must be stored); leaf: any non-zero among the 8^3 own voxels (OpenVDB leaf exists);
-// bbox6 / maxbits: active-voxel bbox and maximum (grid->evalMinMax, CPURenderer.cpp:501-502).
-__device__ __forceinline__ unsigned int float_order_bits(float f)
-{
-    unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__global__ __launch_bounds__(64) void iso_brick_flags(const float* __restrict__ dense, int nx, int ny, int nz,
-                                                     int nbx, int nby, int nbz,
-                                                     uint8_t* flag9, uint8_t* leaf, int* bbox6, unsigned int* maxbits)
-{
-    const int b = blockIdx.x;
-    const int bx = b % nbx, by = (b / nbx) % nby, bz = b / (nbx * nby);
-    const int lane = threadIdx.x;
-    bool any9 = false, any8 = false;
-    int mnx = INT32_MAX, mny = INT32_MAX, mnz = INT32_MAX, mxx = INT32_MIN, mxy = INT32_MIN, mxz = INT32_MIN;
-    unsigned int mb = 0;
-    for (int k = lane; k < ISO_BRICK_VALUES; k += 64) {
-        const int lx = k % 9, ly = (k / 9) % 9, lz = k / 81;
-        const int x = bx * 8 + lx, y = by * 8 + ly, z = bz * 8 + lz;
-        float f = 0.0f;
-        if (x < nx && y < ny && z < nz) f = dense[((size_t)z * ny + y) * nx + x];
-        if (f != 0.0f) {
-            any9 = true;
-            if (lx < 8 && ly < 8 && lz < 8) {
-                any8 = true;
-                mnx = min(mnx, x); mny = min(mny, y); mnz = min(mnz, z);
-                mxx = max(mxx, x); mxy = max(mxy, y); mxz = max(mxz, z);
-                mb = max(mb, float_order_bits(f));
-            }
-        }
-    }
-    const unsigned long long m9 = __ballot(any9), m8 = __ballot(any8);
-    if (m8) {
-        for (int off = 32; off > 0; off >>= 1) {
-            mnx = min(mnx, __shfl_xor(mnx, off)); mny = min(mny, __shfl_xor(mny, off)); mnz = min(mnz, __shfl_xor(mnz, off));
-            mxx = max(mxx, __shfl_xor(mxx, off)); mxy = max(mxy, __shfl_xor(mxy, off)); mxz = max(mxz, __shfl_xor(mxz, off));
-            mb = max(mb, (unsigned int)__shfl_xor((int)mb, off));
-        }
-    }
-    if (lane == 0) {
-        flag9[b] = m9 ? 1 : 0;
-        leaf[b] = m8 ? 1 : 0;
-        if (m8) {
-            atomicMin(&bbox6[0], mnx); atomicMin(&bbox6[1], mny); atomicMin(&bbox6[2], mnz);
-            atomicMax(&bbox6[3], mxx); atomicMax(&bbox6[4], mxy); atomicMax(&bbox6[5], mxz);
-            atomicMax(maxbits, mb);
-        }
-    }
-}
-
-__global__ __launch_bounds__(64) void iso_brick_fill(const float* __restrict__ dense, int nx, int ny, int nz,
-                                                    int nbx, int nby, int nbz,
-                                                    const int32_t* __restrict__ slot, float* __restrict__ bricks)
-{
-    const int b = blockIdx.x;
-    const int s = slot[b];
-    if (s < 0) return;
-    const int bx = b % nbx, by = (b / nbx) % nby, bz = b / (nbx * nby);
-    float* dst = bricks + (size_t)s * ISO_BRICK_STRIDE;
-    for (int k = threadIdx.x; k < ISO_BRICK_STRIDE; k += 64) {
-        float f = 0.0f;
-        if (k < ISO_BRICK_VALUES) {
-            const int lx = k % 9, ly = (k / 9) % 9, lz = k / 81;
-            const int x = bx * 8 + lx, y = by * 8 + ly, z = bz * 8 + lz;
-            if (x < nx && y < ny && z < nz) f = dense[((size_t)z * ny + y) * nx + x];
-        }
-        dst[k] = f;
-    }
-}
-
-// range[b] = (min, max) over the voxels [8b-1, 8b+9]^3 of brick position b; outside the grid counts as 0
-__global__ __launch_bounds__(64) void iso_leaf_range(const float* __restrict__ dense, int nx, int ny, int nz,
-                                                    int nbx, int nby, int nbz, float* __restrict__ range)
-{
-    const int b = blockIdx.x;
-    const int bx = b % nbx, by = (b / nbx) % nby, bz = b / (nbx * nby);
-    float lo = 3.0e38f, hi = -3.0e38f;
-    for (int k = threadIdx.x; k < 11 * 11 * 11; k += 64) {
-        const int lx = k % 11, ly = (k / 11) % 11, lz = k / 121;
-        const int x = bx * 8 - 1 + lx, y = by * 8 - 1 + ly, z = bz * 8 - 1 + lz;
-        float f = 0.0f;
-        if ((unsigned)x < (unsigned)nx && (unsigned)y < (unsigned)ny && (unsigned)z < (unsigned)nz) f = dense[((size_t)z * ny + y) * nx + x];
-        lo = fminf(lo, f); hi = fmaxf(hi, f);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off));
-        hi = fmaxf(hi, __shfl_xor(hi, off));
-    }
-    if (threadIdx.x == 0) { range[2 * (size_t)b] = lo; range[2 * (size_t)b + 1] = hi; }
-}
-
-// nodeRange[n] = (min of the leaf minima, max of the leaf maxima) over the existing leaves of 128^3 node n
-__global__ __launch_bounds__(64) void iso_node_range(const uint8_t* __restrict__ leaf, const float* __restrict__ leafRange,
-                                                    int nbx, int nby, int nbz, int ox, int oy, int oz, int n1x, int n1y, int n1ox, int n1oy, int n1oz,
-                                                    float* __restrict__ nodeRange)
-{
-    const int n = blockIdx.x;
-    const int ax = n % n1x, ay = (n / n1x) % n1y, az = n / (n1x * n1y);
-    float lo = 3.0e38f, hi = -3.0e38f;
-    for (int k = threadIdx.x; k < 4096; k += 64) {
-        // global brick coordinates of the node's k-th leaf position, then local to the stored region
-        const int bx = ((ax + n1ox) << 4) + (k & 15) - (ox >> 3), by = ((ay + n1oy) << 4) + ((k >> 4) & 15) - (oy >> 3),
-                  bz = ((az + n1oz) << 4) + (k >> 8) - (oz >> 3);
-        if ((unsigned)bx >= (unsigned)nbx || (unsigned)by >= (unsigned)nby || (unsigned)bz >= (unsigned)nbz) continue;
-        const size_t b = ((size_t)bz * nby + by) * nbx + bx;
-        if (!leaf[b]) continue;
-        lo = fminf(lo, leafRange[2 * b]); hi = fmaxf(hi, leafRange[2 * b + 1]);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off));
-        hi = fmaxf(hi, __shfl_xor(hi, off));
-    }
-    if (threadIdx.x == 0) { nodeRange[2 * (size_t)n] = lo; nodeRange[2 * (size_t)n + 1] = hi; }
-}
-
-// sparse loads (.vbx brick lists): the tables of the few existing positions are scattered into memset tables
-__global__ __launch_bounds__(256) void iso_scatter_tables(int n, const long long* __restrict__ index, const int32_t* __restrict__ slotv,
-                                                         const uint8_t* __restrict__ leafv, const float* __restrict__ rangev,
-                                                         int32_t* __restrict__ slot, uint8_t* __restrict__ leaf, float* __restrict__ range)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const long long b = index[i];
-    slot[b] = slotv[i];
-    leaf[b] = leafv[i];
-    range[2 * b] = rangev[2 * i];
-    range[2 * b + 1] = rangev[2 * i + 1];
+    if (px.in_image) store_pixel(P, i, j, o);
 }
 
 }  // namespace
 
-void iso_launch_node_range(const uint8_t* leaf, const float* leafRange, int nbx, int nby, int nbz, const int org[3],
-                           int n1x, int n1y, int n1z, const int n1o[3], float* nodeRange, void* stream)
+int iso_launch_render(const IsoRenderParams& p, int variant, void* stream, void* startEvent, void* stopEvent, int waveCap)
 {
-    hipLaunchKernelGGL(iso_node_range, dim3(n1x * n1y * n1z), dim3(64), 0, (hipStream_t)stream, leaf, leafRange, nbx, nby, nbz,
-                       org[0], org[1], org[2], n1x, n1y, n1o[0], n1o[1], n1o[2], nodeRange);
-}
-
-void iso_launch_scatter_tables(int n, const long long* index, const int32_t* slotv, const uint8_t* leafv, const float* rangev,
-                               int32_t* slot, uint8_t* leaf, float* range, void* stream)
-{
-    if (n > 0)
-        hipLaunchKernelGGL(iso_scatter_tables, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, index, slotv, leafv, rangev, slot, leaf, range);
-}
-
-void iso_launch_leaf_range(const float* dense, int nx, int ny, int nz, int nbx, int nby, int nbz, float* range, void* stream)
-{
-    hipLaunchKernelGGL(iso_leaf_range, dim3(nbx * nby * nbz), dim3(64), 0, (hipStream_t)stream, dense, nx, ny, nz, nbx, nby, nbz, range);
-}
-
-void iso_launch_march_flags(const uint8_t* exists, const float* range, int n, double iso, uint8_t* flags, void* stream)
-{
-    if (n > 0) hipLaunchKernelGGL(iso_march_flags, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, exists, range, n, iso, flags);
-}
-
-void iso_launch_render(const IsoRenderParams& p, int variant, void* stream, void* startEvent, void* stopEvent, int waveCap)
-{
-    const int tiles = ((p.W + 7) >> 3) * ((p.H + 7) >> 3);
+    const int tiles = iso_tiles(p.W, p.H);
     const dim3 grid(tiles), block(64);
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0 = (hipEvent_t)startEvent, e1 = (hipEvent_t)stopEvent;
     // the AO loop is a separate instantiation: it costs registers the SR-mode render (aosamples=0) should not pay
-    if (variant == 1) {
-        if (p.aoSamples > 0) hipExtLaunchKernelGGL(iso_render_lds<true>, grid, block, 0, st, e0, e1, 0, p);
-        else hipExtLaunchKernelGGL(iso_render_lds<false>, grid, block, 0, st, e0, e1, 0, p);
-    } else if (variant == 3 && (long long)p.nbx * p.nby * p.nbz <= 32768) {
-        // one workgroup of eight tiles per launch slot; tiles are XCD-remapped inside render_gather_tile, so the eight
-        // tiles of a workgroup are spread -- keep them neighbours instead: the remap is applied to the workgroup
-        const size_t lds = (size_t)p.nbx * p.nby * p.nbz * sizeof(int32_t);
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute((const void*)iso_render_gather_ldsslot<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-            (void)hipFuncSetAttribute((const void*)iso_render_gather_ldsslot<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-            attr = true;
-        }
-        const dim3 g8((tiles + 7) / 8), b8(512);
-        if (p.aoSamples > 0) hipExtLaunchKernelGGL(iso_render_gather_ldsslot<true>, g8, b8, lds, st, e0, e1, 0, p);
-        else hipExtLaunchKernelGGL(iso_render_gather_ldsslot<false>, g8, b8, lds, st, e0, e1, 0, p);
-    } else if (variant == 2) {
+    using Kernel = void (*)(const IsoRenderParams);
+    auto launch = [&](Kernel withAo, Kernel plain, dim3 g, dim3 b, size_t lds) {
+        hipExtLaunchKernelGGL(p.aoSamples > 0 ? withAo : plain, g, b, lds, (hipStream_t)stream, (hipEvent_t)startEvent, (hipEvent_t)stopEvent, 0, p);
+    };
+    switch (variant) {
+    case 1: launch(iso_render_lds<true>, iso_render_lds<false>, grid, block, 0); return 0;
+    case 2: {
         const int waves = waveCap > 0 && waveCap < tiles ? (waveCap + 7) & ~7 : (tiles + 7) & ~7;   // 0 = one wave per tile
-        const dim3 capped(waves / 4), block4(256);                                                  // 4 waves per workgroup
-        (void)hipMemsetAsync(p.tileQueue, 0, 8 * sizeof(unsigned), st);
+        (void)hipMemsetAsync(p.tileQueue, 0, 8 * sizeof(unsigned), (hipStream_t)stream);
         // the one-sample flat traversal: 116 registers on its own, 21 cold values spilled under the 128-register cap
         // (the two-sample form spills 77 and the frame is slower with it: 379 vs 393 frames/s)
-        if (p.aoSamples > 0) hipExtLaunchKernelGGL((iso_render_gather_slim<true, 1>), capped, block4, 0, st, e0, e1, 0, p);
-        else hipExtLaunchKernelGGL((iso_render_gather_slim<false, 1>), capped, block4, 0, st, e0, e1, 0, p);
-    } else if (variant == 4) {
-        if (p.aoSamples > 0) hipExtLaunchKernelGGL((iso_render_gather<true, 0>), grid, block, 0, st, e0, e1, 0, p);
-        else hipExtLaunchKernelGGL((iso_render_gather<false, 0>), grid, block, 0, st, e0, e1, 0, p);
-    } else if (variant == 5) {
-        if (p.aoSamples > 0) hipExtLaunchKernelGGL((iso_render_gather<true, 1>), grid, block, 0, st, e0, e1, 0, p);
-        else hipExtLaunchKernelGGL((iso_render_gather<false, 1>), grid, block, 0, st, e0, e1, 0, p);
-    } else {
-        if (p.aoSamples > 0) hipExtLaunchKernelGGL((iso_render_gather<true, 3>), grid, block, 0, st, e0, e1, 0, p);
-        else hipExtLaunchKernelGGL((iso_render_gather<false, 3>), grid, block, 0, st, e0, e1, 0, p);
+        launch(iso_render_gather_slim<true, 1>, iso_render_gather_slim<false, 1>, dim3(waves / 4), dim3(256), 0);   // 4 waves per workgroup
+        return waves;
+    }
+    case 4: launch(iso_render_gather<true, 0>, iso_render_gather<false, 0>, grid, block, 0); return 0;
+    case 5: launch(iso_render_gather<true, 1>, iso_render_gather<false, 1>, grid, block, 0); return 0;
+    case 3:
+        if ((long long)p.nbx * p.nby * p.nbz <= 32768) {
+            // one workgroup of eight neighbouring tiles per launch slot: the XCD remap is applied to the workgroup, not the tile
+            static bool attr = false;
+            if (!attr) {
+                (void)hipFuncSetAttribute((const void*)iso_render_gather_ldsslot<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+                (void)hipFuncSetAttribute((const void*)iso_render_gather_ldsslot<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+                attr = true;
+            }
+            launch(iso_render_gather_ldsslot<true>, iso_render_gather_ldsslot<false>, dim3((tiles + 7) / 8), dim3(512),
+                   (size_t)p.nbx * p.nby * p.nbz * sizeof(int32_t));
+            return 0;
+        }
+        [[fallthrough]];                                                     // a larger slot table does not fit: variant 0
+    default: launch(iso_render_gather<true, 3>, iso_render_gather<false, 3>, grid, block, 0); return 0;
     }
 }
 
 void iso_launch_render_from_block(const IsoRenderParams& p, const IsoFrameBlock* deviceBlock, void* stream)
 {
-    const int tiles = ((p.W + 7) >> 3) * ((p.H + 7) >> 3);
+    const int tiles = iso_tiles(p.W, p.H);
     hipLaunchKernelGGL(iso_render_gather_block, dim3(tiles), dim3(64), 0, (hipStream_t)stream, p, deviceBlock);
 }
 
@@ -1390,7 +1122,7 @@ void iso_launch_write_block(const IsoFrameBlock& block, IsoFrameBlock* deviceDst
 
 void iso_launch_ao_distances(const IsoRenderParams& p, const double* hitState, const float* gbuf, double* dist, void* stream)
 {
-    const int tiles = ((p.W + 7) >> 3) * ((p.H + 7) >> 3);
+    const int tiles = iso_tiles(p.W, p.H);
     hipLaunchKernelGGL(iso_ao_dist_kernel, dim3(tiles), dim3(64), 0, (hipStream_t)stream, p, hitState, gbuf, dist);
 }
 
@@ -1408,7 +1140,7 @@ void iso_launch_tile_order(const unsigned* cost, unsigned short* order, int n, i
 
 void iso_launch_render_stats(const IsoRenderParams& p, int variant, long long* out, void* stream)
 {
-    const int tiles = ((p.W + 7) >> 3) * ((p.H + 7) >> 3);
+    const int tiles = iso_tiles(p.W, p.H);
     if (variant == 4) hipLaunchKernelGGL(iso_render_stats<0>, dim3(tiles), dim3(64), 0, (hipStream_t)stream, p, out);
     else if (variant == 5) hipLaunchKernelGGL(iso_render_stats<1>, dim3(tiles), dim3(64), 0, (hipStream_t)stream, p, out);
     else hipLaunchKernelGGL(iso_render_stats<3>, dim3(tiles), dim3(64), 0, (hipStream_t)stream, p, out);
@@ -1417,18 +1149,4 @@ void iso_launch_render_stats(const IsoRenderParams& p, int variant, long long* o
 void iso_launch_gate(const unsigned* resident, unsigned target, int timeoutUs, void* stream)
 {
     hipLaunchKernelGGL(iso_gate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, resident, target, (long long)timeoutUs * 100);
-}
-
-void iso_launch_brick_flags(const float* dense, int nx, int ny, int nz, int nbx, int nby, int nbz,
-                            uint8_t* flag9, uint8_t* leaf, int* bbox6, unsigned int* maxbits, void* stream)
-{
-    hipLaunchKernelGGL(iso_brick_flags, dim3(nbx * nby * nbz), dim3(64), 0, (hipStream_t)stream,
-                       dense, nx, ny, nz, nbx, nby, nbz, flag9, leaf, bbox6, maxbits);
-}
-
-void iso_launch_brick_fill(const float* dense, int nx, int ny, int nz, int nbx, int nby, int nbz,
-                           const int32_t* slot, float* bricks, void* stream)
-{
-    hipLaunchKernelGGL(iso_brick_fill, dim3(nbx * nby * nbz), dim3(64), 0, (hipStream_t)stream,
-                       dense, nx, ny, nz, nbx, nby, nbz, slot, bricks);
 }

@@ -59,6 +59,9 @@ struct IsoRenderParams {
     double* hitState;            // [H][W][6] or NULL: (origin xyz, normal xyz) exactly as ambient_occlusion() receives them
 };
 constexpr int ISO_ORDER_MAX_TILES = 4096;
+// a W x H image in 8 x 8 pixel tiles (one wave64 each), ragged ones included
+constexpr int iso_tiles_x(int W) { return (W + 7) >> 3; }
+constexpr int iso_tiles(int W, int H) { return iso_tiles_x(W) * ((H + 7) >> 3); }
 
 // What changes from frame to frame when only the camera moves: a launch that reads this block from DEVICE memory (isoRenderFromBlockAsync)
 // is the same launch every frame -- it can be captured in a HIP graph and replayed (isoWriteFrameBlockAsync refreshes the block).
@@ -83,9 +86,10 @@ struct IsoGvdbFrame {
     float aoRadius;
 };
 
-// launchers (iso_kernels.hip, iso_gvdb.hip)
-// waveCap: variant 2 only -- launch at most this many one-wave workgroups (0 = one per 8x8 tile)
-void iso_launch_render(const IsoRenderParams& p, int variant, void* stream, void* startEvent, void* stopEvent, int waveCap);
+// launchers (iso_kernels.hip, iso_gvdb.hip, iso_build.hip)
+// waveCap: variant 2 only -- launch at most this many waves (0 = one per 8x8 tile).  Returns the number of capped waves
+// launched (0 for every other variant): what P.resident will have grown by once they have all started.
+int iso_launch_render(const IsoRenderParams& p, int variant, void* stream, void* startEvent, void* stopEvent, int waveCap);
 // variant 0 without AO with the camera part of `p` taken from a device-resident block; no dispatch-packet events (graph capture)
 void iso_launch_render_from_block(const IsoRenderParams& p, const IsoFrameBlock* deviceBlock, void* stream);
 // *deviceDst = block, by a one-wave kernel that carries the block as its argument: ordered in `stream` like any launch, no staging buffer to race on
