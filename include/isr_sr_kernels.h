@@ -458,6 +458,43 @@ typedef struct IsrDisplayParams {
 } IsrDisplayParams;
 int isrDisplayFrame(const IsrDisplayParams* params, void* stream);
 
+/* The viewer's frame in its NON-NETWORK render modes (mainGUI.py:712-757: nearest, bilinear, bicubic, ground truth), same file.  The
+ * twelve-channel image is the rendered G-buffer itself -- mask mapped to [-1, +1], colour = clamp(shading, 0, 1) evaluated at the
+ * G-buffer's resolution -- interpolated x4 with all its channels (nothing is clamped afterwards: the bicubic overshoot stays), or taken as
+ * it is (ISR_BASE_IDENTITY: the G-buffer is the full-resolution one).  Focus blend, channel view, post-smoothing and RGBA copy follow as
+ * in isrDisplayFrame (the same device functions); there is no background masking in these modes.
+ *   ISR_BASE_NEAREST / BILINEAR / BICUBIC: TWO launches -- a pre-pass over the h x w pixels writes the planes the view shows into
+ *   `low_planes` (shading each low-resolution pixel once), the display launch interpolates from those planes.  ISR_VIEW_FLOW: one launch.
+ *   ISR_BASE_IDENTITY: ONE launch; `gbuffer` is [H][W][12]; no focus window (it would show the same render), no post-smoothing and no
+ *   flow view (NULL `prev`, `focus`; -1 otherwise).
+ * The arithmetic is isosurfacesuperresolution_amd/viewer.py: compose_baseline (models/videotools.py: upscale_nearest, upscale_bilinear,
+ * upscale_bicubic), operation by operation: the same bits wherever no shading enters.  Returns as isrDisplayFrame. */
+#define ISR_BASE_NEAREST 0
+#define ISR_BASE_BILINEAR 1
+#define ISR_BASE_BICUBIC 2
+#define ISR_BASE_IDENTITY 3
+typedef struct IsrDisplayBaselineParams {
+    const float* gbuffer;       /* [h][w][12] the G-buffer rendered for this frame (mask in [0, 1]); ISR_BASE_IDENTITY: [H][W][12] */
+    float* low_planes;          /* [12][h][w] workspace of the pre-pass (the planes of the view are written); not with ISR_BASE_IDENTITY / ISR_VIEW_FLOW */
+    const float* flow;          /* as IsrDisplayParams from here on */
+    const float* prev;
+    const float* focus;
+    const float* focus_mask;
+    const float* depth_bounds;  /* [2] (min, max) depth of `gbuffer`, whichever resolution it has; ISR_VIEW_DEPTH */
+    float* out;
+    unsigned char* out8;
+    int h, w;                   /* the LOW resolution in every mode: H = 4 h, W = 4 w */
+    int mode;                   /* ISR_BASE_* */
+    int channel;                /* ISR_VIEW_* */
+    float smooth_prev, smooth_cur;
+    int viewport[4];
+    float shading[18];          /* needed by ISR_VIEW_COLOR (every mode) and by the focus window */
+    int exponent;
+    float ao_strength;
+    int enable_specular;
+} IsrDisplayBaselineParams;
+int isrDisplayBaselineFrame(const IsrDisplayBaselineParams* params, void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

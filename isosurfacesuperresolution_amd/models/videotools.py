@@ -147,6 +147,61 @@ class VideoTools:
         return bilinear_taps(image_low, y0, y1, ly, x0, x1, lx)
 
     @staticmethod
+    def upscale_nearest(image_low, upscale_factor):
+        """Nearest-neighbour resize by an integer factor: source index ``dst // r`` on both axes -- ``F.interpolate(mode='nearest')``
+        (ATen ``nearest_neighbor_compute_source_index`` with an exact scale), as index arithmetic."""
+        r = int(upscale_factor)
+        h, w = image_low.shape[-2:]
+        ys = torch.arange(r * h, device=image_low.device) // r
+        xs = torch.arange(r * w, device=image_low.device) // r
+        return image_low.index_select(-2, ys).index_select(-1, xs)
+
+    # The x4 bicubic weights (ATen upsample_bicubic2d, A = -0.75, align_corners=False): src = 0.25 (dst + 0.5) - 0.5, i = floor(src),
+    # t = src - i takes 0.625, 0.875, 0.125, 0.375 for dst % 4 = 0 .. 3; row dst % 4 holds c2(t + 1), c1(t), c1(1 - t), c2(2 - t) with
+    # c1(t) = ((A + 2) t - (A + 3)) t^2 + 1 and c2(t) = ((A t - 5 A) t + 8 A) t - 4 A.  All sixteen are exact in fp32 (and equal to
+    # their float64 values); csrc/sr_display.hip holds the same table.
+    BICUBIC_X4 = ((-0.06591796875, 0.42626953125, 0.74951171875, -0.10986328125),
+                  (-0.01025390625, 0.11474609375, 0.96728515625, -0.07177734375),
+                  (-0.07177734375, 0.96728515625, 0.11474609375, -0.01025390625),
+                  (-0.10986328125, 0.74951171875, 0.42626953125, -0.06591796875))
+
+    @staticmethod
+    def _bicubic_plan(n, dtype, device):
+        """Taps of one axis of the x4 bicubic resize (cached): four index vectors ``i - 1 .. i + 2`` clamped to ``[0, n - 1]`` and the
+        four weight vectors, for the 4 n destination positions."""
+        key = ('bicubic', n, dtype, str(device))
+        plan = VideoTools._offset_cache.get(key)
+        if plan is None:
+            dst = torch.arange(4 * n, device=device)
+            phase = dst % 4
+            i = dst // 4 - (phase < 2).long()                      # floor(0.25 (dst + 0.5) - 0.5)
+            table = torch.tensor(VideoTools.BICUBIC_X4, dtype=dtype, device=device)
+            plan = ([(i - 1 + k).clamp(0, n - 1) for k in range(4)], [table[phase, k] for k in range(4)])
+            VideoTools._offset_cache[key] = plan
+        return plan
+
+    @staticmethod
+    def upscale_bicubic(image_low, upscale_factor):
+        """Bicubic resize x4 as ``F.interpolate(mode='bicubic', align_corners=False)`` defines it (A = -0.75, border taps clamped), with
+        the operations fixed: the horizontal pass first, taps accumulated in order (``r = w0 v0; r = r + w1 v1; ...``, one rounding
+        per operation, no fused multiply-add), then the vertical pass the same way over the four row results -- the order
+        ``csrc/sr_display.hip`` computes in.  Nothing is clamped: the overshoot stays.  Other factors take ``F.interpolate``."""
+        if int(upscale_factor) != 4:
+            return F.interpolate(image_low, scale_factor=upscale_factor, mode='bicubic', align_corners=False)
+        h, w = image_low.shape[-2:]
+        xi, xw = VideoTools._bicubic_plan(w, image_low.dtype, image_low.device)
+        yi, yw = VideoTools._bicubic_plan(h, image_low.dtype, image_low.device)
+        rows = None
+        for k in range(4):
+            term = xw[k] * image_low.index_select(-1, xi[k])
+            rows = term if rows is None else rows + term
+        out = None
+        for k in range(4):
+            term = yw[k].unsqueeze(-1) * rows.index_select(-2, yi[k])
+            out = term if out is None else out + term
+        return out
+
+    @staticmethod
     def warp_upscale_library(image_high, flow_low, upscale_factor, special_mask=False):
         """The same warp through ``F.interpolate`` + ``F.grid_sample`` (the reference's calls, videotools.py:51-87): equal to
         ``warp_upscale`` up to the roundings those kernels choose."""

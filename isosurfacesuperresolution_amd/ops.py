@@ -43,6 +43,14 @@ class _DisplayParams(ctypes.Structure):
         ("exponent", ctypes.c_int), ("ao_strength", ctypes.c_float), ("enable_specular", ctypes.c_int)]
 
 
+class _DisplayBaselineParams(ctypes.Structure):
+    """``IsrDisplayBaselineParams`` of include/isr_sr_kernels.h."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("gbuffer", "low_planes", "flow", "prev", "focus", "focus_mask", "depth_bounds", "out", "out8")] + [
+        ("h", ctypes.c_int), ("w", ctypes.c_int), ("mode", ctypes.c_int), ("channel", ctypes.c_int),
+        ("smooth_prev", ctypes.c_float), ("smooth_cur", ctypes.c_float), ("viewport", ctypes.c_int * 4), ("shading", ctypes.c_float * 18),
+        ("exponent", ctypes.c_int), ("ao_strength", ctypes.c_float), ("enable_specular", ctypes.c_int)]
+
+
 def _bind(lib):
     """ctypes signatures of include/isr_sr_kernels.h on a loaded build of the library (product or diagnostics: the same ABI)."""
     vp, ci, cf, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
@@ -154,6 +162,8 @@ def _bind(lib):
     lib.isrSetTrunkRows.argtypes = [ci]; lib.isrSetTrunkRows.restype = None
     if hasattr(lib, "isrDisplayFrame"):               # (an older build loaded through ISR_SR_LIB for an A/B run has no display stage)
         lib.isrDisplayFrame.argtypes = [ctypes.POINTER(_DisplayParams), vp]; lib.isrDisplayFrame.restype = ci
+    if hasattr(lib, "isrDisplayBaselineFrame"):       # (likewise: the render modes came after the display stage)
+        lib.isrDisplayBaselineFrame.argtypes = [ctypes.POINTER(_DisplayBaselineParams), vp]; lib.isrDisplayBaselineFrame.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -2215,4 +2225,98 @@ def display_frame(gbuffer_hwc, rgb, raw=None, filled_flow=None, shading=None, ch
     rc = _sr().isrDisplayFrame(ctypes.byref(p), _stream())
     if rc != 0:
         raise RuntimeError("isrDisplayFrame failed (%d)" % rc)
+    return out
+
+
+BASELINE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2, "ground_truth": 3}           # ISR_BASE_* (ground truth: IDENTITY)
+
+
+def display_baseline_frame(gbuffer_hwc, mode, shading=None, filled_flow=None, channel="color", focus=None, focus_gbuffer=None, bounds=None,
+                           prev_displayed=None, post_smoothing=0.0, out=None, out8=None, workspace=None):
+    """``viewer.compose_baseline`` on device tensors (``isrDisplayBaselineFrame``): same arguments; -> ``out`` [1,3,4h,4w] (allocated if
+    None; must not be ``prev_displayed``), ``out8`` as ``display_frame``.  ``nearest`` / ``bilinear`` / ``bicubic``: gbuffer [h,w,12],
+    two launches (a low-resolution pre-pass into ``workspace``, [12,h,w] fp32, allocated if None; then the display launch);
+    ``ground_truth``: gbuffer [4h,4w,12], one launch, focus and post-smoothing are not applied and the flow view raises, as in the
+    definition.  ``shading`` is needed by the colour view and by a focus window.  No fall-back: tensors the launch does not take raise."""
+    if mode not in BASELINE_MODES:
+        raise ValueError("mode must be one of %s" % (tuple(BASELINE_MODES),))
+    if channel not in DISPLAY_VIEWS:
+        raise ValueError("channel must be one of %s" % (tuple(DISPLAY_VIEWS),))
+    truth = mode == "ground_truth"
+    if truth:
+        if channel == "flow":
+            raise ValueError("display_baseline_frame: no flow view in ground-truth mode")
+        focus = focus_gbuffer = prev_displayed = None
+    if not (torch.is_tensor(gbuffer_hwc) and gbuffer_hwc.is_cuda and gbuffer_hwc.dtype == torch.float32 and gbuffer_hwc.dim() == 3
+            and gbuffer_hwc.shape[-1] == 12 and gbuffer_hwc.is_contiguous()):
+        raise ValueError("display_baseline_frame: a contiguous fp32 device G-buffer [rows,cols,12] is needed")
+    rows, cols = gbuffer_hwc.shape[0], gbuffer_hwc.shape[1]
+    if truth and (rows % 4 or cols % 4):
+        raise ValueError("display_baseline_frame: the ground-truth G-buffer is [4h,4w,12]")
+    h, w = (rows // 4, cols // 4) if truth else (rows, cols)
+    if not (0 < h <= 16383 and 0 < w <= 16383):
+        raise ValueError("display_baseline_frame: 0 < h, w <= 16383")
+    H, W = 4 * h, 4 * w
+    dev = gbuffer_hwc.device
+    keep = []
+    p = _DisplayBaselineParams()
+    p.gbuffer = gbuffer_hwc.data_ptr()
+    smoothing = prev_displayed is not None and post_smoothing != 0
+    if channel == "flow" or smoothing:
+        if filled_flow is None or tuple(filled_flow.shape) != (1, 2, h, w) or not filled_flow.is_cuda or filled_flow.dtype != torch.float32:
+            raise ValueError("display_baseline_frame: the hole-filled flow [1,2,h,w] is needed (flow view, post-smoothing)")
+        keep.append(filled_flow.contiguous())
+        p.flow = keep[-1].data_ptr()
+    if smoothing:
+        if tuple(prev_displayed.shape) != (1, 3, H, W) or not prev_displayed.is_cuda or prev_displayed.dtype != torch.float32:
+            raise ValueError("display_baseline_frame: prev_displayed must be [1,3,4h,4w] fp32 on the device")
+        keep.append(prev_displayed.contiguous())
+        p.prev = keep[-1].data_ptr()
+        p.smooth_prev = float(np.float32(post_smoothing))
+        p.smooth_cur = float(np.float32(1.0 - post_smoothing))
+    if focus is not None:
+        viewport, mask = focus
+        if focus_gbuffer is None or tuple(focus_gbuffer.shape) != (H, W, 12) or not focus_gbuffer.is_cuda or not focus_gbuffer.is_contiguous() \
+                or focus_gbuffer.dtype != torch.float32:
+            raise ValueError("display_baseline_frame: focus needs the full-resolution G-buffer [4h,4w,12] on the device")
+        if mask.numel() != H * W or not mask.is_cuda or mask.dtype != torch.float32:
+            raise ValueError("display_baseline_frame: the focus mask must be [1,4h,4w] fp32 on the device")
+        keep.append(mask.contiguous())
+        p.focus, p.focus_mask = focus_gbuffer.data_ptr(), keep[-1].data_ptr()
+        x0, y0, x1, y1 = (int(v) for v in viewport)
+        p.viewport = (ctypes.c_int * 4)(max(0, x0), max(0, y0), min(W, x1), min(H, y1))
+    if channel == "color":
+        if shading is None:
+            raise ValueError("display_baseline_frame: the colour view needs the shading")
+        p.shading = (ctypes.c_float * 18)(*shading.packed_parameters())
+        p.exponent, p.ao_strength, p.enable_specular = int(shading._specular_exponent), float(shading._ao), int(bool(shading.enable_specular))
+    if channel == "depth":
+        if bounds is None:
+            d = gbuffer_hwc[..., 7]
+            bounds = torch.stack([(d + (d <= 1e-5).to(d.dtype)).min(), d.max()])
+        if bounds.numel() != 2 or not bounds.is_cuda or bounds.dtype != torch.float32:
+            raise ValueError("display_baseline_frame: bounds must be two fp32 values on the device")
+        keep.append(bounds.contiguous())
+        p.depth_bounds = keep[-1].data_ptr()
+    if not truth and channel != "flow":
+        if workspace is None:
+            workspace = torch.empty((12, h, w), dtype=torch.float32, device=dev)
+        if tuple(workspace.shape) != (12, h, w) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.dtype != torch.float32:
+            raise ValueError("display_baseline_frame: workspace must be a contiguous [12,h,w] fp32 device tensor")
+        p.low_planes = workspace.data_ptr()
+    if out is None:
+        out = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (1, 3, H, W) or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("display_baseline_frame: out must be a contiguous [1,3,4h,4w] fp32 device tensor")
+    if smoothing and out.data_ptr() == p.prev:
+        raise ValueError("display_baseline_frame: out must not be prev_displayed (the warp reads neighbouring pixels)")
+    p.out = out.data_ptr()
+    if out8 is not None:
+        if tuple(out8.shape) != (H, W, 4) or not out8.is_cuda or not out8.is_contiguous() or out8.dtype != torch.uint8:
+            raise ValueError("display_baseline_frame: out8 must be a contiguous [4h,4w,4] uint8 device tensor")
+        p.out8 = out8.data_ptr()
+    p.h, p.w, p.mode, p.channel = h, w, BASELINE_MODES[mode], DISPLAY_VIEWS[channel]
+    rc = _sr().isrDisplayBaselineFrame(ctypes.byref(p), _stream())
+    if rc != 0:
+        raise RuntimeError("isrDisplayBaselineFrame failed (%d)" % rc)
     return out
