@@ -495,6 +495,37 @@ typedef struct IsrDisplayBaselineParams {
 } IsrDisplayBaselineParams;
 int isrDisplayBaselineFrame(const IsrDisplayBaselineParams* params, void* stream);
 
+/* The metric stage of the statistics harness (csrc/sr_metrics.hip; stats.Statistics(metrics="hip")): masked squared error (PSNR), the
+ * MS-SSIM terms and the absolute-difference histogram of one image pair, as utils/psnr.py, utils/ssim.py and np.histogram define them.
+ * Images: fp32 [C][H][W] as pointer + row pitch + plane pitch (in floats; the harness passes border-cropped views), every pixel widened
+ * to fp64 and ALL arithmetic in fp64, operation by operation as the Python definition and with no contraction into FMAs.  `mask` /
+ * `blend`: an optional fp64 plane [H][W] (row pitch in doubles), NULL = none.  `blend` replaces image a by a' = b + m (a - b) first.
+ * Results stay on the device, no entry point synchronises; sums are per-workgroup partial sums in a fixed order followed by a
+ * fixed-order final sum (no floating-point atomics): two calls give the same bits.  Every entry point returns 0, -1 on arguments it
+ * refuses (nothing launched), -2 if a launch failed.
+ *
+ * isrMetricsSqErr: out[0] = sum over c, y, x of (m a - m b)^2 (this order, utils/psnr.py:13; m = 1 without a mask), out[1] = sum of m over
+ *   y, x (H W without a mask).  `workspace`: ISR_METRICS_SQERR_WORKSPACE_BYTES.
+ * isrMetricsMsssim: out[0..4] = mean of the SSIM map of levels 0..4, out[5..9] = mean of v1 / v2 of the same levels
+ *   (utils/ssim.py: ssim(full=True): window k = min(11, H, W) of the level, valid convolution, C1 / C2 from the dynamic range guessed from
+ *   image a' of the level, avg_pool2d(2) between levels), out[10] = prod over i < 4 of (out[5 + i]^w_i out[4]^w_4) (utils/ssim.py:62).
+ *   `windows`: fp64 [5][121], row l = the k x k table utils.ssim.create_window(k) makes for level l (fp32 products widened), applied as a
+ *   full k x k sum.  H, W >= 32 (the definition pools five times).  The level's min / max reaches the SSIM launch through `workspace`
+ *   (isrMetricsMsssimWorkspace bytes; a pure size query): no host read between levels.
+ * isrMetricsAbsDiffHistogram: counts[0..bins-1] = np.histogram(scale * sum over c of |a'_c - b_c|, bins, range=(0, 1)) (channels summed
+ *   left to right: (d0 + d1) + d2), counts[bins] = the number of values inside [0, 1].  Values outside (and NaN) are dropped, 1.0 falls
+ *   into the last bin, the index floor(v bins) is corrected against `edges` = fp64 np.linspace(0, 1, bins + 1).  bins <= 1024. */
+#define ISR_METRICS_SQERR_WORKSPACE_BYTES 16384
+int isrMetricsSqErr(const float* a, long long aRow, long long aPlane, const float* b, long long bRow, long long bPlane,
+                    const double* mask, long long maskRow, int C, int H, int W, void* workspace, double* out, void* stream);
+long long isrMetricsMsssimWorkspace(int C, int H, int W);
+int isrMetricsMsssim(const float* a, long long aRow, long long aPlane, const float* b, long long bRow, long long bPlane,
+                     const double* blend, long long blendRow, int C, int H, int W, const double* windows, void* workspace, double* out,
+                     void* stream);
+int isrMetricsAbsDiffHistogram(const float* a, long long aRow, long long aPlane, const float* b, long long bRow, long long bPlane,
+                               const double* blend, long long blendRow, int C, int H, int W, double scale, int bins, const double* edges,
+                               long long* counts, void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

@@ -164,6 +164,13 @@ def _bind(lib):
         lib.isrDisplayFrame.argtypes = [ctypes.POINTER(_DisplayParams), vp]; lib.isrDisplayFrame.restype = ci
     if hasattr(lib, "isrDisplayBaselineFrame"):       # (likewise: the render modes came after the display stage)
         lib.isrDisplayBaselineFrame.argtypes = [ctypes.POINTER(_DisplayBaselineParams), vp]; lib.isrDisplayBaselineFrame.restype = ci
+    if hasattr(lib, "isrMetricsMsssim"):              # (likewise: the metric stage of the statistics harness, csrc/sr_metrics.hip)
+        cd = ctypes.c_double
+        lib.isrMetricsSqErr.argtypes = [vp, ll, ll, vp, ll, ll, vp, ll, ci, ci, ci, vp, vp, vp]; lib.isrMetricsSqErr.restype = ci
+        lib.isrMetricsMsssimWorkspace.argtypes = [ci, ci, ci]; lib.isrMetricsMsssimWorkspace.restype = ll
+        lib.isrMetricsMsssim.argtypes = [vp, ll, ll, vp, ll, ll, vp, ll, ci, ci, ci, vp, vp, vp, vp]; lib.isrMetricsMsssim.restype = ci
+        lib.isrMetricsAbsDiffHistogram.argtypes = [vp, ll, ll, vp, ll, ll, vp, ll, ci, ci, ci, cd, ci, vp, vp, vp]
+        lib.isrMetricsAbsDiffHistogram.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -2320,3 +2327,135 @@ def display_baseline_frame(gbuffer_hwc, mode, shading=None, filled_flow=None, ch
     if rc != 0:
         raise RuntimeError("isrDisplayBaselineFrame failed (%d)" % rc)
     return out
+
+
+# ---- the metric stage of the statistics harness (csrc/sr_metrics.hip; stats.Statistics(metrics="hip")) ----
+
+METRICS_SQERR_WORKSPACE_BYTES = 16384           # ISR_METRICS_SQERR_WORKSPACE_BYTES
+MSSSIM_LEVELS = 5
+MSSSIM_WINDOW = 11
+
+
+def _image3(t):
+    """[C,H,W] view of an image given as [C,H,W] or [1,C,H,W]; None if it is neither."""
+    if t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]
+    return t if t.dim() == 3 else None
+
+
+def _plane2(t, h, w):
+    """[H,W] view of a mask / blend plane given as [H,W], [1,H,W] or [1,1,H,W]: fp64 on the device, rows dense."""
+    while t.dim() > 2 and t.shape[0] == 1:
+        t = t[0]
+    if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
+        raise ValueError("metrics: the mask / blend plane must be a float64 device tensor [%d, %d] with dense rows" % (h, w))
+    return t
+
+
+def metrics_supported(*tensors):
+    """Can the metric kernels read these images where they lie: fp32 on one device, [C,H,W] or [1,C,H,W] of one shape, dense rows
+    (cropped views are fine: row and plane pitches are passed), non-negative pitches?"""
+    first = None
+    for t in tensors:
+        v = _image3(t) if isinstance(t, torch.Tensor) else None
+        if v is None or not v.is_cuda or v.dtype != torch.float32 or v.numel() == 0:
+            return False
+        c, h, w = v.shape
+        if v.stride(2) != 1 or v.stride(1) < w or v.stride(0) < (1 if c > 1 else 0) or c > 64 or h > 32768 or w > 32768:
+            return False
+        if first is None:
+            first = v
+        elif v.shape != first.shape or v.device != first.device:
+            return False
+    return first is not None
+
+
+def _metric_pair(name, a, b):
+    if not metrics_supported(a, b):
+        raise ValueError("%s: two float32 device images [C,H,W] of one shape with dense rows are needed" % name)
+    a, b = _image3(a), _image3(b)
+    return a, b, (_ptr(a), a.stride(1), a.stride(0), _ptr(b), b.stride(1), b.stride(0))
+
+
+def masked_sq_err(a, b, mask=None):
+    """-> float64 device tensor [2]: sum((m a - m b)^2) over the image and sum(m) over its pixels (``utils/psnr.py:12-13``; without a
+    mask m = 1).  Two launches on the current stream, nothing synchronises; ``psnr_from_sq_err`` turns it into the PSNR."""
+    a, b, views = _metric_pair("masked_sq_err", a, b)
+    c, h, w = a.shape
+    m = _plane2(mask, h, w) if mask is not None else None
+    workspace = torch.empty(METRICS_SQERR_WORKSPACE_BYTES // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty(2, dtype=torch.float64, device=a.device)
+    rc = _sr().isrMetricsSqErr(*views, _ptr(m), m.stride(0) if m is not None else 0, c, h, w, _ptr(workspace), _ptr(out), _stream())
+    if rc != 0:
+        raise RuntimeError("isrMetricsSqErr failed (%d)" % rc)
+    return out
+
+
+def psnr_from_sq_err(sq_err, channels, height, width, masked, epsilon=1e-7):
+    """``utils.PSNR`` from the two sums of ``masked_sq_err``, on the device (a 0-dim float64 tensor)."""
+    mse = sq_err[0] / float(channels * height * width)
+    if not masked:
+        return 10 * torch.log10(1 / (epsilon + mse))
+    return 10 * ((height * width) / sq_err[1]) * torch.log10(1 / (epsilon + mse))          # (the operation order of utils/psnr.py:12-14)
+
+
+def msssim_windows(height, width, device):
+    """float64 [5, 121]: row l holds the k x k table of ``utils.ssim.create_window(k)`` (fp32 products, widened) for MS-SSIM level l of
+    an image of this size, k = min(11, H >> l, W >> l).  Depends on the size only: a caller with many frames keeps it."""
+    from .utils.ssim import create_window
+    table = torch.zeros(MSSSIM_LEVELS, MSSSIM_WINDOW * MSSSIM_WINDOW, dtype=torch.float64)
+    for level in range(MSSSIM_LEVELS):
+        k = min(MSSSIM_WINDOW, height >> level, width >> level)
+        table[level, :k * k] = create_window(k)[0, 0].double().reshape(-1)
+    return table.to(device)
+
+
+def msssim_terms(a, b, blend=None, windows=None):
+    """-> float64 device tensor [11]: the mean SSIM map of the five levels, the mean v1 / v2 of the five levels, and their combination
+    ``utils.ssim.msssim`` (``utils/ssim.py:29-62``), evaluated in fp64 on the fp32 images.  ``blend``: a float64 plane m; image a is
+    replaced by b + m (a - b) first.  ``windows``: ``msssim_windows(H, W, device)`` if the caller kept it.  H, W >= 32."""
+    a, b, views = _metric_pair("msssim_terms", a, b)
+    c, h, w = a.shape
+    if h < 32 or w < 32:
+        raise ValueError("msssim_terms: the five levels need an image of at least 32 x 32, not %d x %d" % (h, w))
+    m = _plane2(blend, h, w) if blend is not None else None
+    if windows is None:
+        windows = msssim_windows(h, w, a.device)
+    if not (windows.is_cuda and windows.dtype == torch.float64 and tuple(windows.shape) == (MSSSIM_LEVELS, MSSSIM_WINDOW ** 2) and windows.is_contiguous()):
+        raise ValueError("msssim_terms: windows must be the float64 device tensor of msssim_windows")
+    lib = _sr()
+    nbytes = lib.isrMetricsMsssimWorkspace(c, h, w)
+    if nbytes <= 0:
+        raise RuntimeError("isrMetricsMsssimWorkspace refuses %d x %d x %d" % (c, h, w))
+    workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty(2 * MSSSIM_LEVELS + 1, dtype=torch.float64, device=a.device)
+    rc = lib.isrMetricsMsssim(*views, _ptr(m), m.stride(0) if m is not None else 0, c, h, w, _ptr(windows), _ptr(workspace), _ptr(out), _stream())
+    if rc != 0:
+        raise RuntimeError("isrMetricsMsssim failed (%d)" % rc)
+    return out
+
+
+def histogram_edges(bins, device):
+    """float64 ``np.linspace(0, 1, bins + 1)`` on the device: the edge table of ``abs_diff_histogram``."""
+    return torch.from_numpy(np.linspace(0.0, 1.0, bins + 1)).to(device)
+
+
+def abs_diff_histogram(a, b, bins, scale=1.0, blend=None, edges=None):
+    """-> int64 device tensor [bins + 1]: ``np.histogram(scale * sum_c |a_c - b_c|, bins, range=(0, 1))`` in fp64 (channels summed left
+    to right) and, last, the number of values inside [0, 1].  ``blend`` as in ``msssim_terms``; ``edges``: ``histogram_edges(bins, device)``
+    if the caller kept it."""
+    a, b, views = _metric_pair("abs_diff_histogram", a, b)
+    c, h, w = a.shape
+    if not 1 <= bins <= 1024:
+        raise ValueError("abs_diff_histogram: 1 .. 1024 bins")
+    m = _plane2(blend, h, w) if blend is not None else None
+    if edges is None:
+        edges = histogram_edges(bins, a.device)
+    if not (edges.is_cuda and edges.dtype == torch.float64 and tuple(edges.shape) == (bins + 1,) and edges.is_contiguous()):
+        raise ValueError("abs_diff_histogram: edges must be the float64 device tensor of histogram_edges(bins)")
+    counts = torch.empty(bins + 1, dtype=torch.int64, device=a.device)
+    rc = _sr().isrMetricsAbsDiffHistogram(*views, _ptr(m), m.stride(0) if m is not None else 0, c, h, w, float(scale), bins, _ptr(edges),
+                                          _ptr(counts), _stream())
+    if rc != 0:
+        raise RuntimeError("isrMetricsAbsDiffHistogram failed (%d)" % rc)
+    return counts
