@@ -421,6 +421,26 @@ void isrSetTrunkPackedResult(int on);      /* 1: isrTrunkDataflow also writes th
  * Environment: ISR_TRUNK_ROWS. */
 void isrSetTrunkRows(int rows);
 
+/* SPLIT-OPERAND stride-2 TRANSPOSED convolution (csrc/sr_conv_transpose.hip): what replaces the library call behind
+ * nn.ConvTranspose2d(64, 64, 3, stride=2, padding=1, output_padding=1) + nn.LeakyReLU of the TecoGAN generator
+ * (SuperresolutionNetwork/models/tecogan.py:55-59):
+ *     y[co][2i + a][2j + b] = act(bias[co] + sum_ci sum_taps x[ci][i + di][j + dj] w[ci][co][ky][kx]),    a, b in {0, 1},
+ * rows a = 0: (ky 1, di 0); a = 1: (ky 2, di 0), (ky 0, di 1); columns alike; input rows >= h and columns >= w contribute nothing.
+ * One image, 64 -> 64 channels, fp32 planes: x [64][h][w] with planes xPlane floats apart, y [64][2h][2w] with planes yPlane floats
+ * apart (rows packed).  Same arithmetic as isrConv3x3ForwardSplit (operands as fp16 (hi, lo) pairs, three fp16 MFMAs per product, fp32
+ * accumulation; |x| < 65520), same range guard (isrSetRangeFlag arms the launch).
+ *   isrConvTransposeSplitPrepare(w [64][64][3][3] fp32 in the ConvTranspose2d layout [ci][co][ky][kx], wq, stream): wq =
+ *     isrConvTransposeSplitWeightBytes() bytes of device memory (layout private to the kernel);
+ *   isrConvTranspose3x3S2ForwardSplit(x, wq, bias [64] or NULL, y, Cin, h, w, Cout, act (NONE / RELU / LEAKY), slope, xPlane, yPlane, stream):
+ *     h, w are the INPUT sizes;
+ *   isrConvTranspose3x3S2SplitSupported(Cin, Cout, h, w, xPlane, yPlane) -> 1 if the launch takes these tensors.
+ * 0 ok, -1 bad arguments, -2 launch failure, -3 unsupported. */
+long long isrConvTransposeSplitWeightBytes(void);
+int isrConvTransposeSplitPrepare(const float* w, void* wq, void* stream);
+int isrConvTranspose3x3S2SplitSupported(int Cin, int Cout, int h, int w, long long xPlane, long long yPlane);
+int isrConvTranspose3x3S2ForwardSplit(const float* x, const void* wq, const float* bias, float* y, int Cin, int h, int w, int Cout,
+                                      int act, float slope, long long xPlane, long long yPlane, void* stream);
+
 /* The DISPLAY STAGE of the viewer's frame in one launch (csrc/sr_display.hip), per high-resolution pixel: what the reference viewer does
  * between the network and the window (SuperresolutionNetwork/mainGUI.py:603-608,626-636,762-853) -- the twelve-channel image (x4
  * bilinear of the low G-buffer with the network's channels in place), background masking, the focus-of-context blend with a

@@ -1,7 +1,8 @@
-"""Generator networks.  ``createNetwork`` mirrors ``SuperresolutionNetwork/models/__init__.py:21-49``;
-only EnhanceNet is on the hot path, the alternative generators
-(SubpixelNet, TecoGAN, RCAN) are out of scope and raise."""
+"""Generator networks.  ``createNetwork`` mirrors ``SuperresolutionNetwork/models/__init__.py:21-49``:
+EnhanceNet and TecoGAN (its stride-2 transposed convolutions on ``ops.conv_transpose3x3_s2``) run on
+the HIP kernels; the other alternative generators (SubpixelNet, RCAN) are out of scope and raise."""
 from .enhancenet import EnhanceNet
+from .tecogan import TecoGAN
 from .videotools import VideoTools
 
 
@@ -13,6 +14,8 @@ def createNetwork(name, upscale_factor, input_channels, channel_mask, output_cha
     key = name.lower()
     if key == 'enhancenet':
         return EnhanceNet(upscale_factor, input_channels, channel_mask, output_channels, additional_opt)
-    if key in ('subpixelnet', 'tecogan', 'rcan'):
+    if key == 'tecogan':
+        return TecoGAN(upscale_factor, input_channels, channel_mask, output_channels, additional_opt)
+    if key in ('subpixelnet', 'rcan'):
         raise NotImplementedError("generator '%s' is outside the accelerated hot path" % name)
     raise ValueError('Unknown model %s' % name)

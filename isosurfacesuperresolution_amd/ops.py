@@ -171,6 +171,12 @@ def _bind(lib):
         lib.isrMetricsMsssim.argtypes = [vp, ll, ll, vp, ll, ll, vp, ll, ci, ci, ci, vp, vp, vp, vp]; lib.isrMetricsMsssim.restype = ci
         lib.isrMetricsAbsDiffHistogram.argtypes = [vp, ll, ll, vp, ll, ll, vp, ll, ci, ci, ci, cd, ci, vp, vp, vp]
         lib.isrMetricsAbsDiffHistogram.restype = ci
+    if hasattr(lib, "isrConvTranspose3x3S2ForwardSplit"):       # (likewise: the transposed convolution, csrc/sr_conv_transpose.hip)
+        lib.isrConvTransposeSplitWeightBytes.argtypes = []; lib.isrConvTransposeSplitWeightBytes.restype = ll
+        lib.isrConvTransposeSplitPrepare.argtypes = [vp, vp, vp]; lib.isrConvTransposeSplitPrepare.restype = ci
+        lib.isrConvTranspose3x3S2SplitSupported.argtypes = [ci, ci, ci, ci, ll, ll]; lib.isrConvTranspose3x3S2SplitSupported.restype = ci
+        lib.isrConvTranspose3x3S2ForwardSplit.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, ll, ll, vp]
+        lib.isrConvTranspose3x3S2ForwardSplit.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -364,7 +370,9 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  32: "conv3x3_wgrad_split_kernel",
                  # the colour networks' frame kernels (33 carries the tail's matrix work; 34-36 are small kernels)
                  33: "conv3x3_split_tail_colour_kernel", 34: "tail_finish_colour_kernel", 35: "assemble_input_colour_kernel",
-                 36: "finish_frame_colour_kernel"}
+                 36: "finish_frame_colour_kernel",
+                 # the transposed convolution of the TecoGAN generator (csrc/sr_conv_transpose.hip)
+                 37: "convt3x3s2_split_kernel"}
 
 
 def debug_switches():
@@ -1418,6 +1426,118 @@ def conv3x3(x, weight, bias=None, act='none', slope=0.01, residual=None, upsampl
     y = _Conv3x3Function.apply(x, weight, bias, residual, act, slope)
     if act == 'relu' and residual is None:
         y._isr_relu_out = True      # a consumer conv3x3 may fold this ReLU's backward into its data gradient
+    return y
+
+
+# ---- stride-2 transposed convolution: TecoGAN's learned x2 upsampling (csrc/sr_conv_transpose.hip) --------------------------------
+_convt_cache = _WeightImages(64)
+
+
+def _prepare_convt(weight):
+    """The [ci, co, 3, 3] weight of a ConvTranspose2d(64, 64, 3, 2, 1, 1) as the split kernel's image, cached like ``_prepare_split``."""
+    lib = _sr()
+    key = (id(weight), "split")
+    wq = _convt_cache.lookup(key, (weight,))
+    if wq is not None:
+        return wq
+    wq = torch.empty(lib.isrConvTransposeSplitWeightBytes(), dtype=torch.uint8, device=weight.device)
+    rc = lib.isrConvTransposeSplitPrepare(_ptr(weight.detach().contiguous()), _ptr(wq), _stream())
+    if rc != 0:
+        raise RuntimeError("isrConvTransposeSplitPrepare failed (%d)" % rc)
+    _convt_cache.store(key, (weight,), wq)
+    return wq
+
+
+def conv_transpose_phase_weight(weight):
+    """The transposed convolution as an ordinary 3x3 convolution with 4 Cout outputs followed by ``F.pixel_shuffle(., 2)``:
+    [4 co + 2 a + b][ci][r][s] holds the taps of output phase (a, b) -- w[ci][co][ky][kx] at r = 1 for ky = 1 (a = 0) and ky = 2
+    (a = 1), at r = 2 for ky = 0 (a = 1); columns alike -- and zeros elsewhere.  The convolution's zero padding below and to the right
+    is the transposed convolution's missing neighbour.  No arithmetic: the same products, four of nine taps structural zeros."""
+    cin, cout = weight.shape[0], weight.shape[1]
+    w = weight.detach().permute(1, 0, 2, 3)                       # [co, ci, ky, kx]
+    e = torch.zeros((cout, 4, cin, 3, 3), dtype=weight.dtype, device=weight.device)
+    taps = {0: ((1, 1),), 1: ((1, 2), (2, 0))}                     # phase bit -> ((r, k), ...)
+    for a in (0, 1):
+        for b in (0, 1):
+            for r, ky in taps[a]:
+                for s, kx in taps[b]:
+                    e[:, 2 * a + b, :, r, s] = w[:, :, ky, kx]
+    return e.reshape(4 * cout, cin, 3, 3)
+
+
+def _conv_transpose_exact(x, weight, bias, act, slope):
+    """The exact fp32 route: the zero-embedded weight on the exact ``isrConv3x3Forward`` kernel, then the pixel shuffle."""
+    key = (id(weight), "embed")
+    hit = _convt_cache.lookup(key, (weight, bias))
+    if hit is None:
+        hit = (conv_transpose_phase_weight(weight), bias.detach().repeat_interleave(4).contiguous() if bias is not None else None)
+        _convt_cache.store(key, (weight, bias), hit)
+    we, be = hit
+    y = _launch_forward(x, prepare_weights(we), be, None, we.shape[1], we.shape[0], act, slope, False, packed=True)
+    return F.pixel_shuffle(y, 2)
+
+
+def _convt_fits(x, weight):
+    n, cin, h, w = x.shape
+    xplane = max(x.stride(1), h * w) if (x.stride(3) == 1 and x.stride(2) == w) else h * w
+    return bool(_sr().isrConvTranspose3x3S2SplitSupported(cin, weight.shape[1], h, w, xplane, 4 * h * w + plane_pad(2 * h, 2 * w)))
+
+
+def conv_transpose3x3_s2_split(x, weight, bias=None, act='none', slope=0.01):
+    """``conv_transpose3x3_s2`` on the split-operand kernel (no autograd; 64 -> 64 channels): one launch per image."""
+    if act not in ('none', 'relu', 'leaky'):
+        raise ValueError("unknown activation %r" % (act,))
+    lib = _sr()
+    with torch.no_grad():
+        n, cin, h, w = x.shape
+        cout = weight.shape[1]
+        x, xp, xi = _plane_strides(x)
+        wq = _prepare_convt(weight)
+        b = bias.detach().contiguous() if bias is not None else None
+        y = empty_planes(n, cout, 2 * h, 2 * w, x.device)
+        key = None
+        for k in range(n):
+            key = _arm_range(id(weight), x.device)
+            rc = lib.isrConvTranspose3x3S2ForwardSplit(ctypes.c_void_p(x.data_ptr() + 4 * k * xi), _ptr(wq), _ptr(b),
+                                                       ctypes.c_void_p(y.data_ptr() + 4 * k * y.stride(0)), cin, h, w, cout,
+                                                       ACT_CODES[act], float(slope), xp, y.stride(1), _stream())
+            if rc != 0:
+                raise RuntimeError("isrConvTranspose3x3S2ForwardSplit failed (%d)" % rc)
+        y._isr_range_key = key
+        return y
+
+
+def conv_transpose3x3_s2(x, weight, bias=None, act='none', slope=0.01):
+    """y = act(conv_transpose2d(x, w, bias, stride=2, padding=1, output_padding=1)): x [N, Cin, h, w], weight [Cin, Cout, 3, 3] (the
+    ``nn.ConvTranspose2d`` layout) -> [N, Cout, 2h, 2w].  TecoGAN's two upsampling layers (64 -> 64).
+
+    * CPU tensors: ``F.conv_transpose2d`` and the activation.
+    * device tensors, no gradient needed: the split-operand kernel ``isrConvTranspose3x3S2ForwardSplit`` (csrc/sr_conv_transpose.hip),
+      its output armed with a range key like ``conv3x3_split``'s.  With the input's range key hot, ``SPLIT_F16`` off or a shape the
+      kernel does not take (channels other than 64, more than 2 GiB): the exact fp32 route -- the four phases as zero-padded 3x3
+      taps of a [4 Cout, Cin, 3, 3] weight on the exact ``conv3x3`` kernel, then ``F.pixel_shuffle``.
+    * under autograd: PyTorch's own transposed convolution (a warning says so, once).  TRAINING a TecoGAN is not on the HIP path -- the
+      transposed convolution has no backward kernels here -- and no GPU test runs this route."""
+    if act not in ('none', 'relu', 'leaky'):
+        raise ValueError("unknown activation %r" % (act,))
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != weight.shape[0]:
+        raise ValueError("conv_transpose3x3_s2: x [N, Cin, h, w] and weight [Cin, Cout, 3, 3] expected")
+    if not x.is_cuda:
+        return _act_cpu(F.conv_transpose2d(x, weight, bias, stride=2, padding=1, output_padding=1), act, slope)
+    if x.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise TypeError("conv_transpose3x3_s2 (HIP) computes in fp32")
+    needs_grad = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
+    if needs_grad:
+        _warn_once("convt_autograd", "conv_transpose3x3_s2: under autograd the transposed convolution runs on PyTorch's own kernels "
+                   "(training a TecoGAN is not on the HIP path)")
+        return _act_cpu(F.conv_transpose2d(x, weight, bias, stride=2, padding=1, output_padding=1), act, slope)
+    hot_in = range_is_hot(getattr(x, '_isr_range_key', None), x.device)
+    if SPLIT_F16 and not hot_in and _convt_fits(x, weight):
+        return conv_transpose3x3_s2_split(x, weight, bias, act, slope)
+    with torch.no_grad():
+        y = _conv_transpose_exact(x, weight, bias, act, slope)
+    if hot_in:
+        y._isr_range_key = HOT          # whatever consumes it stays exact too (its range is not tracked)
     return y
 
 

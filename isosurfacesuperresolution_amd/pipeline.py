@@ -14,6 +14,7 @@ import torch
 
 from . import ops
 from .inference.flowfill import fill_flow
+from .models.tecogan import TecoGAN
 from .utils import ScreenSpaceShading
 from .volumes import fmt3
 
@@ -71,8 +72,13 @@ def run_network_colour(model, x, after_trunk=None, prefetch_point="trunk"):
     and the next frame's ``prev_high`` in one tensor.  The same routing: dataflow trunk -> postblock.1 -> postblock.4 (packed-split
     where ``ops.packed_supported``) -> the three-channel fused tail (``ops.tail_conv_finish_colour`` where ``ops.tail_supported``);
     with a layer on the range guard's exact route, the per-layer kernels and the small-Cout last layer with the colour finishing in
-    its epilogue."""
+    its epilogue.  A colour TecoGAN: ``forward_features`` (per-layer kernels, the transposed convolutions on
+    ``ops.conv_transpose3x3_s2``), then ``ops.finish_frame_colour``; ``x`` is the fp32 input of ``ops.assemble_input_colour``."""
     net = model.model
+    if isinstance(net, TecoGAN):
+        # a colour TecoGAN (fused_path_ok): its own layers -- the last one carries a LeakyReLU, so no finishing is folded into it --
+        # then reconstruction + clamp as one launch
+        return ops.finish_frame_colour(net.forward_features(x, after_trunk=after_trunk), x)
     last, six = net.postblock[8], net.postblock[6]
     f4, after_trunk, _f2 = _walk_to_tail(net, x, after_trunk, prefetch_point, (3, 64, 3, 3), packed_tail=False)
     if isinstance(f4, ops.PackedSplit) or (f4 is not None and ops.tail_supported(f4, six.weight, last.weight)):
@@ -132,10 +138,16 @@ def is_colour(model):
 
 def fused_path_ok(model, upscale=4):
     """The fused frame kernels take this network: 4x, residual reconstruction over the five input channels -- or, a colour model, over
-    [0, 1, 2] with three outputs, bilinear upsampling and no batch norm."""
+    [0, 1, 2] with three outputs, bilinear upsampling and no batch norm (EnhanceNet) / a last convolution 64 -> 3 (TecoGAN)."""
     net = model.model
     if upscale != 4 or getattr(net, 'recon_type', None) != 'residual' or getattr(net, 'channel_mask', None) is None:
         return False
+    if isinstance(net, TecoGAN):
+        # (a pickled reference object has no ``output_channels`` / ``use_bn``: the last convolution says what comes out; an unshaded
+        #  TecoGAN exists with direct reconstruction only and takes the module route)
+        last = net.postblock[4]
+        return is_colour(model) and list(net.channel_mask) == [0, 1, 2] and net.upsample == 'bilinear' \
+            and (last.in_channels, last.out_channels) == (64, 3) and model.input_channels - 48 in ops.COLOUR_VARIANTS
     if is_colour(model):
         return list(net.channel_mask) == [0, 1, 2] and getattr(net, 'output_channels', None) == 3 \
             and getattr(net, 'upsample', None) == 'bilinear' and not getattr(net, 'use_bn', True) and hasattr(net, 'forward_features') \

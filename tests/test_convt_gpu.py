@@ -1,0 +1,201 @@
+"""GPU: the stride-2 transposed convolution of the TecoGAN generator -- ``ops.conv_transpose3x3_s2`` on
+``isrConvTranspose3x3S2ForwardSplit`` (csrc/sr_conv_transpose.hip) -- against ``F.conv_transpose2d`` in fp64 on the CPU.
+
+The kernel's tile is 4 x 32 low-resolution pixels (one halo row below, one halo column to the right); 16-byte stores need an even
+width, odd widths take dword stores.  Shapes: 1 x 1; 3 x 5; 4 x 32 (exactly one tile) and 5 x 33 (one over in both directions: the
+halo comes from a neighbour tile, the last tiles are ragged, odd width); 8 x 32 and 9 x 33 (the same for the 8 x 32 tiling of the
+other split kernels); 17 x 40 (several tiles both ways, even width)."""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (3, 5), (4, 32), (5, 33), (8, 32), (9, 33), (17, 40)]
+KERNEL = "convt3x3s2_split_kernel"
+
+
+def _ref64(x, w, b=None):
+    return F.conv_transpose2d(x.double(), w.double(), None if b is None else b.double(), stride=2, padding=1, output_padding=1)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(h, w):
+    """Unit-scale input with both signs, weights at the He scale of the fixtures (sqrt(2 / (9 * 64))), a bias, and the fp64 result
+    WITHOUT bias (computed once per shape; bias and activation are applied to it in fp64 per variant)."""
+    g = torch.Generator().manual_seed(1000 * h + w)
+    x = torch.randn(1, 64, h, w, generator=g)
+    wt = torch.randn(64, 64, 3, 3, generator=g) * (2.0 / (9 * 64)) ** 0.5
+    b = torch.randn(64, generator=g) * 0.05
+    return x, wt, b, _ref64(x, wt)
+
+
+def _phases(err):
+    return {"(%d,%d)" % (a, b): float(err[..., a::2, b::2].max()) for a in (0, 1) for b in (0, 1)}
+
+
+@pytest.mark.parametrize("h,w", SHAPES)
+def test_transposed_convolution_matches_fp64(h, w):
+    from isosurfacesuperresolution_amd import ops
+    x, wt, b, pre = _case(h, w)
+    xd, wd, bd = x.cuda(), wt.cuda(), b.cuda()
+    assert (x < 0).any() and (x > 0).any()
+    ops.profile_enable(True)
+    try:
+        with torch.no_grad():
+            outs = {(hb, act): ops.conv_transpose3x3_s2(xd, wd, bd if hb else None, act=act) for hb in (True, False) for act in ('none', 'leaky')}
+        torch.cuda.synchronize()
+        names = [n for n, _, _ in ops.profile_records()]
+    finally:
+        ops.profile_enable(False)
+    assert names == [KERNEL] * 4, names                                   # the new kernel, not another route
+    for (hb, act), y in outs.items():
+        ref = pre + b.double().view(1, 64, 1, 1) if hb else pre
+        if act == 'leaky':
+            assert 0.3 < (ref < 0).double().mean().item() < 0.7               # the leaky branch is exercised
+            ref = F.leaky_relu(ref, 0.01)
+        assert y.shape == (1, 64, 2 * h, 2 * w) and y._isr_range_key is not None
+        err = (y.double().cpu() - ref).abs()
+        print("convT %dx%d bias=%s act=%s: max %.3g, per phase %s" % (h, w, hb, act, err.max().item(), _phases(err)))
+        assert err.max().item() <= 1e-4, "per-phase maximum error %s" % _phases(err)
+
+
+def test_batch_and_padded_planes():
+    """Several images (one launch each) and an input whose channel planes are padded (``ops.empty_planes`` of a producer)."""
+    from isosurfacesuperresolution_amd import ops
+    x, wt, b, _ = _case(9, 33)
+    xs = torch.cat([x, -0.5 * x, x.flip(3)], dim=0)
+    padded = torch.zeros(3, 64, 9 * 33 + 16).cuda()
+    view = padded.as_strided((3, 64, 9, 33), (64 * (9 * 33 + 16), 9 * 33 + 16, 33, 1))
+    view.copy_(xs)
+    with torch.no_grad():
+        y = ops.conv_transpose3x3_s2(view, wt.cuda(), b.cuda(), act='leaky')
+    ref = F.leaky_relu(_ref64(xs, wt, b), 0.01)
+    err = (y.double().cpu() - ref).abs()
+    assert err.max().item() <= 1e-4, _phases(err)
+
+
+def _integer_case(h, w, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randint(-2, 3, (1, 64, h, w), generator=g).float()
+    wt = torch.randint(-3, 4, (64, 64, 3, 3), generator=g).float()
+    b = torch.randint(-4, 5, (64,), generator=g).float()
+    taps = wt.reshape(64 * 64, 9).t()
+    assert all(not torch.equal(taps[i], taps[k]) for i in range(9) for k in range(i))     # every tap differs from every other
+    return x, wt, b
+
+
+@pytest.mark.parametrize("h,w", [(9, 33), (6, 34), (4, 32)])
+def test_small_integers_are_exact(h, w):
+    """Inputs in {-2..2}, weights in {-3..3}, integer bias; slope 0.5: everything is exact in fp16 and every sum stays below 2^24, so
+    the result equals the fp64 one bit for bit -- a wrong tap, flip, phase, edge or lane exchange cannot hide inside a tolerance."""
+    from isosurfacesuperresolution_amd import ops
+    x, wt, b = _integer_case(h, w, seed=h * 100 + w)
+    ref = _ref64(x, wt, b)
+    assert ref.abs().max().item() < 2 ** 24
+    with torch.no_grad():
+        y = ops.conv_transpose3x3_s2(x.cuda(), wt.cuda(), b.cuda())
+        yl = ops.conv_transpose3x3_s2(x.cuda(), wt.cuda(), b.cuda(), act='leaky', slope=0.5)
+        y0 = ops.conv_transpose3x3_s2(x.cuda(), wt.cuda(), None)
+    assert torch.equal(y.cpu(), ref.float()), _phases((y.double().cpu() - ref).abs())
+    assert torch.equal(yl.cpu(), F.leaky_relu(ref, 0.5).float())
+    assert torch.equal(y0.cpu(), _ref64(x, wt).float())
+
+
+@pytest.mark.parametrize("h,w", [(5, 7), (6, 8), (5, 34)])
+def test_one_hot_at_each_corner_is_exact(h, w):
+    """A single 1 at each of the four corners (one image each, different input channels): the output is the tap pattern itself."""
+    from isosurfacesuperresolution_amd import ops
+    _, wt, b = _integer_case(3, 3, seed=7)
+    x = torch.zeros(4, 64, h, w)
+    for n, (i, j, ci) in enumerate([(0, 0, 0), (0, w - 1, 17), (h - 1, 0, 40), (h - 1, w - 1, 63)]):
+        x[n, ci, i, j] = 1.0
+    with torch.no_grad():
+        y = ops.conv_transpose3x3_s2(x.cuda(), wt.cuda(), b.cuda())
+    ref = _ref64(x, wt, b)
+    assert torch.equal(y.cpu(), ref.float()), _phases((y.double().cpu() - ref).abs())
+
+
+def test_hot_input_takes_the_exact_route():
+    """|x| ~ 1e5 overflows the fp16 split; with the input's range key hot the layer runs on the exact fp32 kernels (the phases as
+    zero-padded 3x3 taps + pixel shuffle) and its output stays hot."""
+    from isosurfacesuperresolution_amd import ops
+    x, wt, b, _ = _case(9, 33)
+    x = x * 1.0e5
+    xd = x.cuda()
+    xd._isr_range_key = ops.HOT
+    ops.profile_enable(True)
+    try:
+        with torch.no_grad():
+            y = ops.conv_transpose3x3_s2(xd, wt.cuda(), b.cuda(), act='leaky')
+        torch.cuda.synchronize()
+        names = [n for n, _, _ in ops.profile_records()]
+    finally:
+        ops.profile_enable(False)
+    assert KERNEL not in names and names, names
+    assert y._isr_range_key == ops.HOT and torch.isfinite(y).all()
+    ref = F.leaky_relu(_ref64(x, wt, b), 0.01)
+    assert x.abs().max().item() > 65520
+    rel = (y.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
+    print("exact route: relative error %.3g" % rel)
+    assert rel <= 1e-4
+    # SPLIT_F16 off: the same route for an ordinary input
+    x1, _, _, pre = _case(9, 33)
+    old = ops.SPLIT_F16
+    ops.SPLIT_F16 = False
+    try:
+        with torch.no_grad():
+            y1 = ops.conv_transpose3x3_s2(x1.cuda(), wt.cuda(), None)
+    finally:
+        ops.SPLIT_F16 = old
+    assert (y1.double().cpu() - pre).abs().max().item() <= 1e-4
+
+
+def test_range_guard_routes_a_transposed_convolution_behind_a_hot_producer():
+    """The guard end to end, as tests/test_range_gpu.py does for ``conv3x3``: a badly scaled producer (activations up to ~1e6), the
+    split kernel's overflow is loud, ``refresh_range_flags`` marks the producer hot, and the SAME call then runs exactly."""
+    from isosurfacesuperresolution_amd import ops
+    ops.range_reset()
+    g = torch.Generator().manual_seed(4)
+    x = torch.rand(1, 64, 9, 33, generator=g).cuda()
+    w1 = ((torch.rand(64, 64, 3, 3, generator=g) - 0.5) * 0.05).cuda() * 1.0e6           # the badly scaled layer
+    _, wt, b, _ = _case(9, 33)
+    wd, bd = wt.cuda(), b.cuda()
+    with torch.no_grad():
+        t = ops.conv3x3(x, w1, act='relu')
+        assert t.abs().max().item() > 65520 and torch.isfinite(t).all()
+        y1 = ops.conv_transpose3x3_s2(t, wd, bd, act='leaky')                           # split consumer: overflow, loud
+        assert not torch.isfinite(y1).all()
+        new = ops.refresh_range_flags(x.device)
+        assert id(w1) in new and ops.any_hot(x.device)
+        t = ops.conv3x3(x, w1, act='relu')
+        y2 = ops.conv_transpose3x3_s2(t, wd, bd, act='leaky')                           # now the exact route
+        assert y2._isr_range_key == ops.HOT
+    ref = F.leaky_relu(_ref64(t.cpu(), wt, b), 0.01)
+    assert torch.isfinite(y2).all()
+    assert (y2.double().cpu() - ref).abs().max().item() <= 1e-4 * ref.abs().max().item()
+    ops.range_reset()
+    assert not ops.any_hot(x.device)
+
+
+def test_weight_image_is_cached_and_invalidated():
+    """The kernel-layout image is made once per weight tensor; a change behind autograd's version counter is picked up after
+    ``ops.invalidate_weight_images()`` (both routes)."""
+    from isosurfacesuperresolution_amd import ops
+    x, wt, b, pre = _case(3, 5)
+    xd, wd = x.cuda(), wt.cuda()
+    hot = x.cuda()
+    hot._isr_range_key = ops.HOT
+    with torch.no_grad():
+        y1 = ops.conv_transpose3x3_s2(xd, wd)
+        e1 = ops.conv_transpose3x3_s2(hot, wd)
+        wd.data.mul_(2.0)                                          # in place, the tensor's own version counter does not move
+        assert torch.equal(ops.conv_transpose3x3_s2(xd, wd), y1)   # still the cached image
+        ops.invalidate_weight_images()
+        y2 = ops.conv_transpose3x3_s2(xd, wd)
+        e2 = ops.conv_transpose3x3_s2(hot, wd)
+    assert not torch.equal(y2, y1)
+    assert (y2.double().cpu() - 2 * pre).abs().max().item() <= 2e-4
+    assert (e1.double().cpu() - pre).abs().max().item() <= 1e-4 and (e2.double().cpu() - 2 * pre).abs().max().item() <= 2e-4
