@@ -441,6 +441,31 @@ int isrConvTranspose3x3S2SplitSupported(int Cin, int Cout, int h, int w, long lo
 int isrConvTranspose3x3S2ForwardSplit(const float* x, const void* wq, const float* bias, float* y, int Cin, int h, int w, int Cout,
                                       int act, float slope, long long xPlane, long long yPlane, void* stream);
 
+/* BACKWARD of that layer (training).  With z the pre-activation output, gz = gy act'(y) (the rule of isrActBackward) and the PHASE-MAJOR
+ * gradient G[n][4 co + 2 a + b][i][j] = gz[n][co][2i + a][2j + b] -- low-resolution planes in the order of F.pixel_unshuffle(., 2):
+ *   isrConvTransposePhaseGradient(gy [N][C][2h][2w], y (same shape; NULL with act NONE), G [N][4C][h][w], N, C, h, w, act (NONE / RELU /
+ *     LEAKY), slope, stream): the activation's backward written phase-major (csrc/sr_train.hip); bit-identical to isrActBackward followed
+ *     by pixel_unshuffle.  All tensors packed.
+ *   data gradient gx[n][ci][i][j] = sum_{co,ky,kx} gz[n][co][2i - 1 + ky][2j - 1 + kx] w[ci][co][ky][kx] (rows / columns -1 are outside):
+ *     isrConvTransposeDataGradPrepare(w [64][64][3][3] in the ConvTranspose2d layout, wq, stream): wq = isrConvTransposeDataGradWeightBytes()
+ *       bytes of device memory (layout private to the kernel; NOT the forward image);
+ *     isrConvTranspose3x3S2DataGradSplit(G [N][256][h][w], wq, gx [N][64][h][w], N, C = 64, h, w, stream): convt3x3s2_dgrad_split_kernel, the
+ *       forward kernel's split-operand arithmetic over G, nine 64 x 64 products per low-resolution pixel, sums in a fixed order (the same
+ *       bits on every run).  Honours isrSetMaxSlots (the per-wave maxima of gx) and isrSetRangeFlag.
+ *     isrConvTranspose3x3S2DataGradSplitSupported(N, C, h, w) -> 1 if the launch takes these tensors (C = 64; one image of G below 2 GiB).
+ *   weight / bias gradient: isrConv3x3WeightGradSegments[Split[Max]] on (x, G) as a 64 -> 256 3x3 layer; the 9 live taps of 36 are the
+ *     ConvTranspose2d weight's gradient (ops.conv_transpose_weight_from_phase), gb[co] the sum of its four phase entries.
+ * 0 ok, -1 bad arguments, -2 launch failure, -3 unsupported. */
+/* The TRAINING forward: N packed images in ONE launch of the same kernel (x [N][64][h][w], y [N][64][2h][2w]); a batch of small crops
+ * launched image by image leaves most of the GPU idle. */
+int isrConvTranspose3x3S2ForwardSplitBatch(const float* x, const void* wq, const float* bias, float* y, int N, int h, int w,
+                                           int act, float slope, void* stream);
+int isrConvTransposePhaseGradient(const float* gy, const float* y, float* G, int N, int C, int h, int w, int act, float slope, void* stream);
+long long isrConvTransposeDataGradWeightBytes(void);
+int isrConvTransposeDataGradPrepare(const float* w, void* wq, void* stream);
+int isrConvTranspose3x3S2DataGradSplitSupported(int N, int C, int h, int w);
+int isrConvTranspose3x3S2DataGradSplit(const float* G, const void* wq, float* gx, int N, int C, int h, int w, void* stream);
+
 /* The DISPLAY STAGE of the viewer's frame in one launch (csrc/sr_display.hip), per high-resolution pixel: what the reference viewer does
  * between the network and the window (SuperresolutionNetwork/mainGUI.py:603-608,626-636,762-853) -- the twelve-channel image (x4
  * bilinear of the low G-buffer with the network's channels in place), background masking, the focus-of-context blend with a

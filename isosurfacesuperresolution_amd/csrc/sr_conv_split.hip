@@ -1144,6 +1144,14 @@ static unsigned* g_range_flag = nullptr;
 static unsigned* g_max_slots = nullptr;   // isrSetMaxSlots: per-wave maxima of the NEXT isrConv3x3ForwardSplit launch
 static int g_max_slot_cap = 0, g_max_slot_used = 0;
 unsigned* isr_take_range_flag() { unsigned* f = g_range_flag; g_range_flag = nullptr; return f; }
+unsigned* isr_take_max_slots(int* capacity)
+{
+    unsigned* const words = g_max_slots;
+    *capacity = g_max_slot_cap;
+    g_max_slots = nullptr; g_max_slot_cap = 0; g_max_slot_used = 0;
+    return words;
+}
+void isr_note_max_slot_words(int words) { g_max_slot_used = words; }
 [[maybe_unused]] static unsigned long long* g_split_stamps = nullptr;
 [[maybe_unused]] static int g_split_dbg = 0;
 static int g_split_small = 1;     // 2-row-tile kernel for small images (isrDebugSetSplitSmall)

@@ -24,6 +24,9 @@
 // in registers (one DPP move each), after which the even lane holds four consecutive pixels of channel c and the odd lane the same four
 // of channel c + 1: one 16-byte store per lane, a wave instruction writes four runs of 256 contiguous bytes.  (w odd, or planes that
 // are not 16-byte aligned: dword stores.)
+//
+// Training: the same kernel over a whole batch in one launch (convt3x3s2_split_kernel<true>), and the DATA GRADIENT
+// (convt3x3s2_dgrad_split_kernel, below) over the phase-major output gradient that isrConvTransposePhaseGradient (sr_train.hip) writes.
 #include "sr_split_common.h"
 
 namespace {
@@ -46,6 +49,8 @@ struct ConvTParams {
     int act; float slope;
     int wide;                         // 1: w even, yPlane % 4 == 0, y 16-byte aligned -- the 16-byte stores
     unsigned* absmax;                 // range guard (may be NULL), as SplitConvParams::absmax
+    int tilesImage;                   // BATCH form (training: N images in one launch): tiles per image, floats between images
+    long long xImage, yImage;
 };
 
 // the neighbour lane's value (lane ^ 1): DPP quad_perm [1, 0, 3, 2]
@@ -55,6 +60,9 @@ __device__ __forceinline__ float ct_swap1(float v)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0xB1, 0xF, 0xF, false));
 }
 
+// BATCH: the grid covers N images (image bid / tilesImage, tile bid % tilesImage) -- the training forward: one launch per frame of a batch of
+// clips, not one per clip
+template <bool BATCH>
 __global__ __launch_bounds__(S_THREADS, 2) void convt3x3s2_split_kernel(const ConvTParams p)
 {
     extern __shared__ u32x4 patch[];                                         // CT_PUNITS patch units, then the weight buffer
@@ -66,10 +74,18 @@ __global__ __launch_bounds__(S_THREADS, 2) void convt3x3s2_split_kernel(const Co
         const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
     }
+    const float* xbase = p.x;
+    float* ybase = p.y;
+    if constexpr (BATCH) {
+        const int n = bid / p.tilesImage;
+        bid -= n * p.tilesImage;
+        xbase += (size_t)n * p.xImage;
+        ybase += (size_t)n * p.yImage;
+    }
     const int tx = bid % p.tilesX, ty = bid / p.tilesX;
     const int oy0 = ty * CT_H, ox0 = tx * CT_W;                              // low-resolution origin of the tile
 
-    const rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)((size_t)CT_C * p.xPlane * 4), 0x00020000);
+    const rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xbase), 0, (int)((size_t)CT_C * p.xPlane * 4), 0x00020000);
     const unsigned planeBytes = (unsigned)p.xPlane * 4u;
     u32x4* const wbuf = patch + CT_PUNITS;
 
@@ -166,7 +182,7 @@ __global__ __launch_bounds__(S_THREADS, 2) void convt3x3s2_split_kernel(const Co
     // ---- epilogue: act(acc 2^-S + bias) at (2 ly + a, 2 lx + b).  D row (cout) = (reg & 3) + 8 (reg >> 2) + 4 hh, column (pixel) = j.
     const float unscale = reinterpret_cast<const float*>(p.wq)[1];          // 2^-S (header of the prepared weights)
     const int W2 = 2 * p.w;
-    const rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)((size_t)CT_C * p.yPlane * 4), 0x00020000);
+    const rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(ybase, 0, (int)((size_t)CT_C * p.yPlane * 4), 0x00020000);
     const int ly = oy0 + wave, lx = ox0 + j;
     const bool inside = ly < p.h && lx < p.w;
     const bool odd = (j & 1) != 0;
@@ -225,6 +241,172 @@ __global__ __launch_bounds__(S_THREADS, 2) void convt3x3s2_split_kernel(const Co
     isr_range_note(p.absmax, mag);
 }
 
+// ---- DATA GRADIENT ----------------------------------------------------------------------------------------------------------------
+// gx[ci][i][j] = sum_{co, ky, kx} gz[co][2i - 1 + ky][2j - 1 + kx] w[ci][co][ky][kx] over the PHASE-MAJOR gradient G[4 co + 2 a + b][i][j] =
+// gz[co][2i + a][2j + b] (isrConvTransposePhaseGradient): tap ky = 1 reads phase a = 0 at row i, ky = 2 reads a = 1 at row i, ky = 0 reads
+// a = 1 at row i - 1; columns alike.  The forward kernel's dataflow with the halo row and column ABOVE and to the LEFT (index -1 is outside
+// the image: zero), the roles of ci and co swapped in the weight image, and ONE accumulator set instead of four: the nine 64 x 64 products
+// of a low-resolution pixel all land on the same output pixel.
+//
+// Structure: workgroup = 4 x 32 low-resolution pixels of one image x 64 output channels (ci), 4 waves, wave w owns row w: 2 channel blocks
+// = 32 accumulator registers.  K runs phase-major: 8 chunks of (phase, 32 co) staged as LDS[hi | lo'][group of 8 co][5 x 33 patch pixels],
+// two k-steps of 16 co each; a k-step of phase (a, b) multiplies that phase's 1, 2, 2 or 4 taps, each against its own neighbour (di, dj) in
+// {0, -1}^2.  Weights [hi | lo][tap slot][lane half][64 ci] of one k-step pass through LDS, fetched into registers under the previous
+// k-step's MFMAs.  Fixed summation order, no atomics on floats: the same bits on every run.  37.5 KB of LDS.
+constexpr int ISR_VARIANT_CONVT_DGRAD = 38;                                  // convt3x3s2_dgrad_split_kernel (ops.VARIANT_NAMES)
+constexpr int DG_WPART = 4 * 2 * 64;                                         // weights of one k-step, one part: [tap slot 0 .. 3][lane half][64 ci]
+constexpr int DG_WUNITS = 2 * DG_WPART;
+constexpr int DG_LDS_BYTES = (CT_PUNITS + DG_WUNITS) * 16;                   // 21 120 + 16 384 = 37 504
+
+struct ConvTGradParams {
+    const float* g; const u32x4* wq; float* gx;
+    int h, w;                         // low-resolution size: G is [N][256][h][w], gx [N][64][h][w], both packed
+    int tilesX, tilesY, tilesImage;
+    unsigned* absmax;                 // range guard (may be NULL)
+    unsigned* slotmax;                // per-wave maxima (may be NULL), as SplitConvParams::slotmax
+};
+
+// tap slot s of phase ph = 2 a + b: the tap 3 ky + kx it multiplies and the patch offset of the neighbour (di, dj) it reads
+__device__ __forceinline__ void dg_slot(int ph, int s, int& tap, int& off)
+{
+    const int a = ph >> 1, b = ph & 1;
+    const int sj = b ? (a ? (s & 1) : s) : 0;                                // 1: the column to the left (kx = 0)
+    const int si = a ? (b ? (s >> 1) : s) : 0;                               // 1: the row above (ky = 0)
+    const int ky = a ? (si ? 0 : 2) : 1, kx = b ? (sj ? 0 : 2) : 1;
+    tap = 3 * ky + kx;
+    off = -(si * CP_W + sj);
+}
+
+__global__ __launch_bounds__(S_THREADS, 2) void convt3x3s2_dgrad_split_kernel(const ConvTGradParams p)
+{
+    extern __shared__ u32x4 patch[];                                         // CT_PUNITS patch units, then the weight buffer
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, hh = lane >> 5;
+    int bid;
+    {   // an XCD (= an L2) gets a contiguous range of tiles
+        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
+    }
+    const int n = bid / p.tilesImage, t = bid - n * p.tilesImage;
+    const int tx = t % p.tilesX, ty = t / p.tilesX;
+    const int oy0 = ty * CT_H, ox0 = tx * CT_W;                              // origin of the tile; the patch starts one row and column before it
+    const int plane = p.h * p.w;
+
+    const rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.g + (size_t)n * 4 * CT_C * plane), 0, (int)((size_t)4 * CT_C * plane * 4), 0x00020000);
+    const unsigned planeBytes = (unsigned)plane * 4u;
+    u32x4* const wbuf = patch + CT_PUNITS;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[cb][i] = 0.0f;
+
+    // step = 4 ph + ks: k-step ks (16 co) of phase ph.  Its weights: up to 4 tap slots x 256 units [part][lane half][64 ci]; thread t moves unit
+    // t of every slot: byte 16 t + 4096 (4 tap + ks) of the prepared image
+    const rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(p.wq + 1), 0, 9 * CT_KSTEPS * 4096, 0x00020000);
+    u32x4* const wdst = wbuf + (tid >> 7) * DG_WPART + (tid & 127);
+    u32x4 wreg[4];
+    auto wfetch = [&](int step) {
+        if (step >= 4 * CT_KSTEPS) return;
+        const int ph = step >> 2, ks = step & 3, nt = (1 + (ph >> 1)) * (1 + (ph & 1));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int tap, off;
+            dg_slot(ph, i, tap, off);
+            if (i < nt) wreg[i] = __builtin_amdgcn_raw_buffer_load_b128(wrs, tid * 16, (tap * CT_KSTEPS + ks) * 4096, 0);
+        }
+    };
+    auto wpark = [&](int step) {
+        const int ph = step >> 2, nt = (1 + (ph >> 1)) * (1 + (ph & 1));
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < nt) wdst[i * 128] = wreg[i];
+    };
+    wfetch(0);                                                               // in flight under the first staging
+
+#pragma unroll 1
+    for (int q = 0; q < 8; ++q) {
+        const int ph = q >> 1, co0 = (q & 1) * S_CHUNK, nt = (1 + (ph >> 1)) * (1 + (ph & 1));
+        // ---- stage 32 co of phase ph, split into hi and lo' parts: unit = (group g of 8 co, patch pixel); rows oy0 - 1 .. oy0 + 3, columns
+        //      ox0 - 1 .. ox0 + 31, zeros outside the image (the buffer load of the out-of-range offset returns 0)
+        for (int u0 = tid; u0 < CT_PART; u0 += 3 * S_THREADS) {
+            float v[3][8];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int u = u0 + k * S_THREADS;
+                const int g = u / CP_PIX, pix = u - g * CP_PIX;
+                const int r = pix / CP_W, c = pix - r * CP_W;
+                const int iy = oy0 - 1 + r, ix = ox0 - 1 + c;
+                const bool ok = u < CT_PART && iy >= 0 && ix >= 0 && iy < p.h && ix < p.w;
+                const unsigned base = (unsigned)(4 * (co0 + g * 8) + ph) * planeBytes + (unsigned)(iy * p.w + ix) * 4u;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[k][e] = buf_load(grs, ok ? base + (unsigned)(4 * e) * planeBytes : BAD_OFFSET);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int u = u0 + k * S_THREADS;
+                f16x8 qh, ql;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { _Float16 a, b; split16x(v[k][e], a, b); qh[e] = a; ql[e] = b; }
+                if (u < CT_PART) { patch[u] = __builtin_bit_cast(u32x4, qh); patch[CT_PART + u] = __builtin_bit_cast(u32x4, ql); }
+            }
+        }
+        wpark(2 * q);                                                        // (its readers passed the barrier that ended the previous chunk)
+        __syncthreads();
+#pragma unroll 1
+        for (int S = 0; S < 2; ++S) {
+            wfetch(2 * q + S + 1);                                           // the next k-step's weights travel under these MFMAs
+            const u32x4* wl = wbuf + hh * 64 + j;
+            const u32x4* bl = patch + (2 * S + hh) * CP_PIX + (wave + 1) * CP_W + (j + 1);
+#pragma unroll 1
+            for (int s = 0; s < nt; ++s) {
+                int tap, off;
+                dg_slot(ph, s, tap, off);
+                const f16x8 bh = __builtin_bit_cast(f16x8, bl[off]);
+                const f16x8 bo = __builtin_bit_cast(f16x8, bl[CT_PART + off]);
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                    const f16x8 ah = __builtin_bit_cast(f16x8, wl[s * 128 + cb * 32]);
+                    const f16x8 al = __builtin_bit_cast(f16x8, wl[DG_WPART + s * 128 + cb * 32]);
+                    const f16x8 as = ah * (_Float16)0.00048828125f;          // w_hi 2^-11: partner of the scaled g_lo'
+                    acc[cb] = mfma16(al, bh, acc[cb]);
+                    acc[cb] = mfma16(as, bo, acc[cb]);
+                    acc[cb] = mfma16(ah, bh, acc[cb]);
+                }
+            }
+            __syncthreads();                                                 // weight buffer (and, after the chunk's last k-step, the patch) free
+            if (S == 0) { wpark(2 * q + 1); __syncthreads(); }
+        }
+    }
+
+    // ---- epilogue: acc 2^-S at (ly, lx).  D row (ci) = (reg & 3) + 8 (reg >> 2) + 4 hh, column (pixel) = j: a wave instruction writes two
+    //      runs of 128 contiguous bytes
+    const float unscale = reinterpret_cast<const float*>(p.wq)[1];
+    const rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(p.gx + (size_t)n * CT_C * plane, 0, (int)((size_t)CT_C * plane * 4), 0x00020000);
+    const int ly = oy0 + wave, lx = ox0 + j;
+    const bool inside = ly < p.h && lx < p.w;
+    const unsigned pixoff = (unsigned)(ly * p.w + lx) * 4u;
+    unsigned mag = 0u;
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int ci = cb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            const float v = acc[cb][i] * unscale;
+            if (inside) mag = isr_umax(mag, isr_mag(v));
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yrs, (int)(inside ? pixoff + (unsigned)ci * planeBytes : BAD_OFFSET), 0, 0);
+        }
+    if (p.slotmax) {
+        unsigned m = mag;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = isr_umax(m, (unsigned)__shfl_xor((int)m, o, 64));
+        if (lane == 0) atomicMax(p.slotmax + blockIdx.x * 4 + wave, m);
+    }
+    isr_range_note(p.absmax, mag);
+}
+
 // header unit of the prepared weights, as isrConvSplitPrepare's: { 2^S, 2^-S, S (int), 0 } with max |w| 2^S in [2^13, 2^14)
 __global__ __launch_bounds__(1024) void convt_scale_kernel(const float* __restrict__ w, int count, u32x4* __restrict__ wq)
 {
@@ -254,6 +436,8 @@ __global__ __launch_bounds__(1024) void convt_scale_kernel(const float* __restri
 
 // w[ci][co][ky][kx] fp32 (the ConvTranspose2d layout) -> wq[1 + ((((tap * 4 + k-step) * 2 + part) * 2 + lane half h) * 64 + cout)][8 x fp16];
 // element e of (k-step s, half h) is input channel 16 s + 8 h + e; part 0 = hi, 1 = lo of w 2^S.  No flip: tap = 3 ky + kx as stored.
+// DGRAD: the data gradient's image -- the same layout with the roles swapped: the 64 rows are ci, element e is co = 16 s + 8 h + e.
+template <bool DGRAD>
 __global__ __launch_bounds__(256) void convt_prepare_kernel(const float* __restrict__ w, u32x4* __restrict__ wq)
 {
     const float scale = reinterpret_cast<const float*>(wq)[0];
@@ -265,7 +449,7 @@ __global__ __launch_bounds__(256) void convt_prepare_kernel(const float* __restr
     for (int e = 0; e < 8; ++e) {
         const int ci = 16 * s + 8 * h + e;
         _Float16 a, b;
-        split16(w[((size_t)ci * CT_C + co) * 9 + tap] * scale, a, b);
+        split16(w[(DGRAD ? (size_t)co * CT_C + ci : (size_t)ci * CT_C + co) * 9 + tap] * scale, a, b);
         qh[e] = a; ql[e] = b;
     }
     const size_t base = 1 + (size_t)(((tap * CT_KSTEPS + s) * 2 + 0) * 2 + h) * CT_C + co;
@@ -281,6 +465,15 @@ bool convt_supported(int Cin, int Cout, int h, int w, long long xPlane, long lon
     return xPlane * CT_C * 4 <= 0x7fffffffLL && yPlane * CT_C * 4 <= 0x7fffffffLL;
 }
 
+// the data gradient: N images, G [N][256][h][w] and gx [N][64][h][w] packed; one image of G through 32-bit buffer offsets
+bool convt_dgrad_supported(int N, int C, int h, int w)
+{
+    if (C != CT_C || N <= 0 || h <= 0 || w <= 0 || h > 16384 || w > 16384) return false;
+    if ((long long)h * w * 4 * CT_C * 4 > 0x7fffffffLL) return false;
+    const long long grid = (long long)N * ((w + CT_W - 1) / CT_W) * ((h + CT_H - 1) / CT_H);
+    return grid <= 0x3fffffffLL;
+}
+
 } // namespace
 
 extern "C" {
@@ -291,8 +484,45 @@ int isrConvTransposeSplitPrepare(const float* w, void* wq, void* stream)
 {
     if (!w || !wq) return -1;
     hipLaunchKernelGGL(convt_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, CT_C * CT_C * 9, (u32x4*)wq);
-    hipLaunchKernelGGL(convt_prepare_kernel, dim3((9 * CT_KSTEPS * 2 * CT_C + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (u32x4*)wq);
+    hipLaunchKernelGGL(convt_prepare_kernel<false>, dim3((9 * CT_KSTEPS * 2 * CT_C + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (u32x4*)wq);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+long long isrConvTransposeDataGradWeightBytes(void) { return CT_WBYTES; }
+
+int isrConvTransposeDataGradPrepare(const float* w, void* wq, void* stream)
+{
+    if (!w || !wq) return -1;
+    hipLaunchKernelGGL(convt_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, CT_C * CT_C * 9, (u32x4*)wq);
+    hipLaunchKernelGGL(convt_prepare_kernel<true>, dim3((9 * CT_KSTEPS * 2 * CT_C + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (u32x4*)wq);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrConvTranspose3x3S2DataGradSplitSupported(int N, int C, int h, int w)
+{
+    return convt_dgrad_supported(N, C, h, w) ? 1 : 0;
+}
+
+int isrConvTranspose3x3S2DataGradSplit(const float* G, const void* wq, float* gx, int N, int C, int h, int w, void* stream)
+{
+    unsigned* const rangeFlag = isr_take_range_flag();       // taken first: an error return must not leave it armed
+    int slotCap = 0;
+    unsigned* const slots = isr_take_max_slots(&slotCap);    // (likewise)
+    if (!G || !wq || !gx) return -1;
+    if (!convt_dgrad_supported(N, C, h, w)) return -3;
+    ConvTGradParams p;
+    p.g = G; p.wq = (const u32x4*)wq; p.gx = gx;
+    p.h = h; p.w = w;
+    p.tilesX = (w + CT_W - 1) / CT_W; p.tilesY = (h + CT_H - 1) / CT_H;
+    p.tilesImage = p.tilesX * p.tilesY;
+    p.absmax = rangeFlag;
+    const long long grid = (long long)N * p.tilesImage;
+    p.slotmax = nullptr;
+    if (slots && 4 * grid <= slotCap) { p.slotmax = slots; isr_note_max_slot_words((int)(4 * grid)); }
+    // algorithmic flops: 2 x 9 channel-mixing products of 64 x 64 per low-resolution pixel
+    const double flops = 2.0 * 9 * CT_C * CT_C * (double)N * h * w;
+    return isr_launch(ISR_VARIANT_CONVT_DGRAD, flops, convt3x3s2_dgrad_split_kernel, dim3((unsigned)grid), dim3(S_THREADS), DG_LDS_BYTES,
+                      (hipStream_t)stream, p);
 }
 
 int isrConvTranspose3x3S2SplitSupported(int Cin, int Cout, int h, int w, long long xPlane, long long yPlane)
@@ -315,9 +545,34 @@ int isrConvTranspose3x3S2ForwardSplit(const float* x, const void* wq, const floa
     p.act = act; p.slope = slope;
     p.wide = ((w & 1) == 0 && (yPlane & 3) == 0 && ((uintptr_t)y & 15) == 0) ? 1 : 0;
     p.absmax = rangeFlag;
+    p.tilesImage = p.tilesX * p.tilesY; p.xImage = 0; p.yImage = 0;
     // algorithmic flops: 2 x 9 channel-mixing products of 64 x 64 per low-resolution pixel
     const double flops = 2.0 * 9 * CT_C * CT_C * (double)h * w;
-    return isr_launch(ISR_VARIANT_CONVT_SPLIT, flops, convt3x3s2_split_kernel, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(S_THREADS), CT_LDS_BYTES,
+    return isr_launch(ISR_VARIANT_CONVT_SPLIT, flops, convt3x3s2_split_kernel<false>, dim3((unsigned)(p.tilesX * p.tilesY)), dim3(S_THREADS), CT_LDS_BYTES,
+                      (hipStream_t)stream, p);
+}
+
+int isrConvTranspose3x3S2ForwardSplitBatch(const float* x, const void* wq, const float* bias, float* y, int N, int h, int w,
+                                           int act, float slope, void* stream)
+{
+    unsigned* const rangeFlag = isr_take_range_flag();       // taken first: an error return must not leave it armed
+    if (!x || !wq || !y || N <= 0 || h <= 0 || w <= 0) return -1;
+    if (act != ISR_ACT_NONE && act != ISR_ACT_RELU && act != ISR_ACT_LEAKY) return -1;
+    const long long xPlane = (long long)h * w, yPlane = 4 * xPlane;
+    if (!convt_supported(CT_C, CT_C, h, w, xPlane, yPlane)) return -3;
+    ConvTParams p;
+    p.x = x; p.wq = (const u32x4*)wq; p.bias = bias; p.y = y;
+    p.h = h; p.w = w;
+    p.xPlane = (int)xPlane; p.yPlane = (int)yPlane;
+    p.tilesX = (w + CT_W - 1) / CT_W; p.tilesY = (h + CT_H - 1) / CT_H;
+    p.act = act; p.slope = slope;
+    p.wide = ((w & 1) == 0 && ((uintptr_t)y & 15) == 0) ? 1 : 0;           // (packed: every plane and image starts 4 h w floats after the last)
+    p.absmax = rangeFlag;
+    p.tilesImage = p.tilesX * p.tilesY; p.xImage = CT_C * xPlane; p.yImage = CT_C * yPlane;
+    const long long grid = (long long)N * p.tilesImage;
+    if (grid > 0x3fffffffLL) return -3;
+    const double flops = 2.0 * 9 * CT_C * CT_C * (double)N * h * w;
+    return isr_launch(ISR_VARIANT_CONVT_SPLIT, flops, convt3x3s2_split_kernel<true>, dim3((unsigned)grid), dim3(S_THREADS), CT_LDS_BYTES,
                       (hipStream_t)stream, p);
 }
 

@@ -80,3 +80,7 @@ static inline void isr_lds_opt_in(int bytes)
 // Range guard (SplitConvParams::absmax): isrSetRangeFlag(ptr) arms the NEXT launch of a split-operand kernel (any translation
 // unit) with a device word that receives the bit pattern of the largest |value| it stores; the launcher takes (and clears) it.
 unsigned* isr_take_range_flag();
+// Per-wave maxima (SplitConvParams::slotmax): isrSetMaxSlots(words, capacity) arms the NEXT launch of a kernel that supports them (any
+// translation unit); the launcher takes (and clears) the array and, if it uses it, says how many words (isrTakeMaxSlotWords reports that).
+unsigned* isr_take_max_slots(int* capacity);
+void isr_note_max_slot_words(int words);

@@ -721,6 +721,44 @@ __global__ __launch_bounds__(256) void recurrent_input_post_kernel(const RecurPa
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Phase-major gradient of the stride-2 transposed convolution (csrc/sr_conv_transpose.hip)
+// ---------------------------------------------------------------------------------------------------------
+// G[n][4 c + 2 a + b][i][j] = gz[n][c][2i + a][2j + b], gz = gy where y > 0 (or no activation), gy * slope elsewhere (slope 0 for
+// ReLU): the rule -- and the expression -- of act_backward_kernel, written in the order of F.pixel_unshuffle(., 2).  A thread per
+// low-resolution pixel: two 8-byte reads per operand (V2; dword reads for planes that are not 8-byte aligned), four dword stores that are
+// contiguous across the threads of a row.
+template <bool V2>
+__global__ __launch_bounds__(256) void convt_phase_grad_kernel(const float* __restrict__ gy, const float* __restrict__ y, float* __restrict__ G,
+                                                                int h, int w, long long count, int act, float slope)
+{
+    const float s = act == ISR_ACT_RELU ? 0.f : slope;
+    const long long plane = (long long)h * w;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < count; q += (long long)gridDim.x * 256) {
+        const int j = (int)(q % w);
+        const long long r = q / w;
+        const int i = (int)(r % h);
+        const long long nc = r / h;                                           // n C + c
+        const long long src = (nc * 2 * h + 2 * i) * (2LL * w) + 2 * j;
+        float* dst = G + nc * 4 * plane + (long long)i * w + j;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const long long e = src + (long long)a * 2 * w;
+            float g0, g1, o0 = 1.f, o1 = 1.f;
+            if constexpr (V2) {
+                const float2 g = *reinterpret_cast<const float2*>(gy + e);
+                g0 = g.x; g1 = g.y;
+                if (y) { const float2 o = *reinterpret_cast<const float2*>(y + e); o0 = o.x; o1 = o.y; }
+            } else {
+                g0 = gy[e]; g1 = gy[e + 1];
+                if (y) { o0 = y[e]; o1 = y[e + 1]; }
+            }
+            dst[(2 * a) * plane] = (act == ISR_ACT_NONE || o0 > 0.f) ? g0 : g0 * s;
+            dst[(2 * a + 1) * plane] = (act == ISR_ACT_NONE || o1 > 0.f) ? g1 : g1 * s;
+        }
+    }
+}
+
 } // namespace
 
 // One Adam step (torch.optim.Adam: no weight decay, no amsgrad) over FLAT parameter / gradient / moment buffers: the whole
@@ -883,6 +921,21 @@ int isrReconResidualBackward(const float* gy, float* gx, int N, int Cout, int Ci
     const long long blocks = (count8 + 255) / 256;
     if (blocks > 0x7fffffffLL) return -1;
     hipLaunchKernelGGL(recon_residual_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, gy, gx, Cout, Cin, k, h, w, count8);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrConvTransposePhaseGradient(const float* gy, const float* y, float* G, int N, int C, int h, int w, int act, float slope, void* stream)
+{
+    if (!gy || !G || N <= 0 || C <= 0 || h <= 0 || w <= 0) return -1;
+    if (act != ISR_ACT_NONE && act != ISR_ACT_RELU && act != ISR_ACT_LEAKY) return -1;
+    if (act != ISR_ACT_NONE && !y) return -1;
+    if (act == ISR_ACT_NONE) y = nullptr;
+    const long long count = (long long)N * C * h * w;
+    long long blocks = (count + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    const bool v2 = !(((uintptr_t)gy | (uintptr_t)y) & 7);                    // (rows are 2 w floats: every pair starts on an even element)
+    hipLaunchKernelGGL(v2 ? convt_phase_grad_kernel<true> : convt_phase_grad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       gy, y, G, h, w, count, act, slope);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

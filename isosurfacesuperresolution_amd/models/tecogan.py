@@ -13,8 +13,9 @@ output: there is no concatenation, so a residual TecoGAN needs ``len(channel_mas
 with three outputs; the unshaded family, mask [0..4] with six outputs, exists only with ``reconType='direct'``).
 
 A pickled reference object carries only ``upscale_factor, upsample, recon_type, num_residual_layers, channel_mask`` (unpickling
-bypasses ``__init__``): nothing else is read here; channel counts come from the convolutions.  Training a TecoGAN is not on the HIP
-path (``ops.conv_transpose3x3_s2`` runs PyTorch's transposed convolution under autograd)."""
+bypasses ``__init__``): nothing else is read here; channel counts come from the convolutions.  Training runs on the HIP path too:
+under autograd ``ops.conv_transpose3x3_s2`` is one node on the transposed convolution's own forward, phase-gradient and data-gradient
+kernels, its weight gradient deferred like every other layer's (``train.backward``)."""
 import torch.nn as nn
 import torch.nn.functional as F
 

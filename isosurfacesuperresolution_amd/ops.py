@@ -177,6 +177,14 @@ def _bind(lib):
         lib.isrConvTranspose3x3S2SplitSupported.argtypes = [ci, ci, ci, ci, ll, ll]; lib.isrConvTranspose3x3S2SplitSupported.restype = ci
         lib.isrConvTranspose3x3S2ForwardSplit.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, ll, ll, vp]
         lib.isrConvTranspose3x3S2ForwardSplit.restype = ci
+    if hasattr(lib, "isrConvTranspose3x3S2DataGradSplit"):      # (likewise: its backward -- phase-major gradient and data gradient)
+        lib.isrConvTransposePhaseGradient.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, cf, vp]; lib.isrConvTransposePhaseGradient.restype = ci
+        lib.isrConvTranspose3x3S2ForwardSplitBatch.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]
+        lib.isrConvTranspose3x3S2ForwardSplitBatch.restype = ci
+        lib.isrConvTransposeDataGradWeightBytes.argtypes = []; lib.isrConvTransposeDataGradWeightBytes.restype = ll
+        lib.isrConvTransposeDataGradPrepare.argtypes = [vp, vp, vp]; lib.isrConvTransposeDataGradPrepare.restype = ci
+        lib.isrConvTranspose3x3S2DataGradSplitSupported.argtypes = [ci, ci, ci, ci]; lib.isrConvTranspose3x3S2DataGradSplitSupported.restype = ci
+        lib.isrConvTranspose3x3S2DataGradSplit.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]; lib.isrConvTranspose3x3S2DataGradSplit.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -372,7 +380,7 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  33: "conv3x3_split_tail_colour_kernel", 34: "tail_finish_colour_kernel", 35: "assemble_input_colour_kernel",
                  36: "finish_frame_colour_kernel",
                  # the transposed convolution of the TecoGAN generator (csrc/sr_conv_transpose.hip)
-                 37: "convt3x3s2_split_kernel"}
+                 37: "convt3x3s2_split_kernel", 38: "convt3x3s2_dgrad_split_kernel"}
 
 
 def debug_switches():
@@ -1009,10 +1017,13 @@ class deferred_weight_gradients:
     def _finish(pending, exc_type):
         if exc_type is not None:
             return False
-        for (_, shape), (weight, bias, xs, gzs) in pending.items():
-            if _weight_grad_into_grad(xs, gzs, weight, bias):
+        for key, (weight, bias, xs, gzs) in pending.items():
+            if len(key) > 2:         # a transposed convolution: (x, phase-major gradient) pairs, the gradient gathered into its own layout
+                gw, gb = _convt_weight_grad(xs, gzs, weight, bias is not None)
+            elif _weight_grad_into_grad(xs, gzs, weight, bias):
                 continue
-            gw, gb = _weight_grad(xs, gzs, weight, bias is not None)
+            else:
+                gw, gb = _weight_grad(xs, gzs, weight, bias is not None)
             for param, g in ((weight, gw), (bias, gb)):
                 if param is None or g is None or not param.requires_grad:
                     continue
@@ -1071,8 +1082,9 @@ def _has_grad_hooks(p):
     return p is not None and bool(getattr(p, '_backward_hooks', None) or getattr(p, '_post_accumulate_grad_hooks', None))
 
 
-def _weight_grad_or_defer(weight, bias, has_bias, x, gz):
+def _weight_grad_or_defer(weight, bias, has_bias, x, gz, convt=False):
     """Inside deferred_weight_gradients(): record the pair and return (None, None); else compute (dw, db) now.
+    ``convt``: ``weight`` is a ConvTranspose2d weight [ci, co, 3, 3] and ``gz`` the phase-major gradient (``_convt_weight_grad``).
 
     Deferred gradients are written to ``param.grad`` when the context exits, AFTER ``loss.backward()`` and without
     passing through autograd's accumulation: tensor hooks and post-accumulate-grad hooks (DDP-style reducers,
@@ -1081,11 +1093,12 @@ def _weight_grad_or_defer(weight, bias, has_bias, x, gz):
     through autograd as usual); ``torch.autograd.grad`` on convolution weights must be called outside the context."""
     if _deferred is not None and weight.is_leaf and (bias is None or bias.is_leaf) \
             and not _has_grad_hooks(weight) and not _has_grad_hooks(bias):
-        entry = _deferred.setdefault((id(weight), tuple(x.shape)), (weight, bias, [], []))
+        key = (id(weight), tuple(x.shape), "convt") if convt else (id(weight), tuple(x.shape))
+        entry = _deferred.setdefault(key, (weight, bias, [], []))
         entry[2].append(x)
         entry[3].append(gz)
         return None, None
-    return _weight_grad([x], [gz], weight, has_bias)
+    return (_convt_weight_grad if convt else _weight_grad)([x], [gz], weight, has_bias)
 
 
 # A residual block of a batch of SMALL images (the 32 x 32 training crops: too few 8 x 32 tiles for the streaming kernel) as ONE
@@ -1433,19 +1446,25 @@ def conv3x3(x, weight, bias=None, act='none', slope=0.01, residual=None, upsampl
 _convt_cache = _WeightImages(64)
 
 
-def _prepare_convt(weight):
-    """The [ci, co, 3, 3] weight of a ConvTranspose2d(64, 64, 3, 2, 1, 1) as the split kernel's image, cached like ``_prepare_split``."""
+def _prepare_convt(weight, layout="split"):
+    """The [ci, co, 3, 3] weight of a ConvTranspose2d(64, 64, 3, 2, 1, 1) as the split kernel's image, cached like ``_prepare_split``.
+    ``layout``: "split" the forward kernel's image, "dgrad" the data-gradient kernel's (ci and co trade places)."""
     lib = _sr()
-    key = (id(weight), "split")
+    key = (id(weight), layout)
     wq = _convt_cache.lookup(key, (weight,))
     if wq is not None:
         return wq
-    wq = torch.empty(lib.isrConvTransposeSplitWeightBytes(), dtype=torch.uint8, device=weight.device)
-    rc = lib.isrConvTransposeSplitPrepare(_ptr(weight.detach().contiguous()), _ptr(wq), _stream())
+    size, prepare = (lib.isrConvTransposeDataGradWeightBytes, lib.isrConvTransposeDataGradPrepare) if layout == "dgrad" else \
+        (lib.isrConvTransposeSplitWeightBytes, lib.isrConvTransposeSplitPrepare)
+    wq = torch.empty(size(), dtype=torch.uint8, device=weight.device)
+    rc = prepare(_ptr(weight.detach().contiguous()), _ptr(wq), _stream())
     if rc != 0:
-        raise RuntimeError("isrConvTransposeSplitPrepare failed (%d)" % rc)
+        raise RuntimeError("%s failed (%d)" % ("isrConvTransposeDataGradPrepare" if layout == "dgrad" else "isrConvTransposeSplitPrepare", rc))
     _convt_cache.store(key, (weight,), wq)
     return wq
+
+
+_CONVT_TAPS = {0: ((1, 1),), 1: ((1, 2), (2, 0))}                 # phase bit -> ((r, k), ...): embedded row / column r holds tap k
 
 
 def conv_transpose_phase_weight(weight):
@@ -1465,16 +1484,47 @@ def conv_transpose_phase_weight(weight):
     return e.reshape(4 * cout, cin, 3, 3)
 
 
-def _conv_transpose_exact(x, weight, bias, act, slope):
-    """The exact fp32 route: the zero-embedded weight on the exact ``isrConv3x3Forward`` kernel, then the pixel shuffle."""
+def conv_transpose_weight_from_phase(dwe):
+    """The exact adjoint of ``conv_transpose_phase_weight``: [4 co, ci, 3, 3] (the gradient of the embedded weight) -> [ci, co, 3, 3],
+    the 9 live taps of 36 gathered -- every (ky, kx) sits at exactly one (phase, r, s); the 27 structural zeros' gradients are dropped.
+    No arithmetic."""
+    cout, cin = dwe.shape[0] // 4, dwe.shape[1]
+    d = dwe.reshape(cout, 4, cin, 3, 3)
+    live = {}
+    for a in (0, 1):
+        for b in (0, 1):
+            for r, ky in _CONVT_TAPS[a]:
+                for s, kx in _CONVT_TAPS[b]:
+                    live[3 * ky + kx] = d[:, 2 * a + b, :, r, s]
+    return torch.stack([live[t] for t in range(9)], dim=0).permute(2, 1, 0).reshape(cin, cout, 3, 3).contiguous()
+
+
+def _convt_embedded(weight, bias):
+    """(We [4 co, ci, 3, 3], be [4 co] or None): ``conv_transpose_phase_weight`` and the bias repeated per phase, cached."""
     key = (id(weight), "embed")
     hit = _convt_cache.lookup(key, (weight, bias))
     if hit is None:
         hit = (conv_transpose_phase_weight(weight), bias.detach().repeat_interleave(4).contiguous() if bias is not None else None)
         _convt_cache.store(key, (weight, bias), hit)
-    we, be = hit
+    return hit
+
+
+def _conv_transpose_exact(x, weight, bias, act, slope):
+    """The exact fp32 route: the zero-embedded weight on the exact ``isrConv3x3Forward`` kernel, then the pixel shuffle."""
+    we, be = _convt_embedded(weight, bias)
     y = _launch_forward(x, prepare_weights(we), be, None, we.shape[1], we.shape[0], act, slope, False, packed=True)
     return F.pixel_shuffle(y, 2)
+
+
+def _convt_weight_grad(xs, gs, weight, has_bias):
+    """(dW [ci, co, 3, 3], db [co]) of a transposed convolution summed over the pairs (xs[k] [N, ci, h, w], gs[k] the phase-major
+    gradient [N, 4 co, h, w]): the segment kernels of ``_weight_grad`` on the pair as a ci -> 4 co 3x3 layer (4x the needed matrix
+    work: 27 of the 36 taps are structural zeros of the embedded weight), then the live taps gathered
+    (``conv_transpose_weight_from_phase``) and the bias gradient summed over the four phases."""
+    cin, cout = weight.shape[0], weight.shape[1]
+    like = weight.detach().new_empty((4 * cout, cin, 3, 3))           # shape and device of the embedded layer (never read)
+    dwe, dbe = _weight_grad(xs, gs, like, has_bias)
+    return conv_transpose_weight_from_phase(dwe), (dbe.view(cout, 4).sum(dim=1) if dbe is not None else None)
 
 
 def _convt_fits(x, weight):
@@ -1507,6 +1557,123 @@ def conv_transpose3x3_s2_split(x, weight, bias=None, act='none', slope=0.01):
         return y
 
 
+# Training route of the transposed convolution: "kernel" -- the dedicated forward and data-gradient kernels (csrc/sr_conv_transpose.hip);
+# "embedded" -- forward and data gradient as the zero-embedded 64 -> 256 3x3 layer on the convolution's own training kernels
+# (``_train_conv``: 4x the matrix work); "torch" -- PyTorch's own transposed convolution under autograd, with its warning (the route
+# before these kernels existed).  The last two are what tools/bench_tecogan_train.py measures the kernels against.  The weight gradient
+# takes the embedded form on both HIP routes.  With TRAIN_SPLIT off both are the embedded layer on the exact fp32 kernels.
+CONVT_TRAIN_ROUTE = os.environ.get("ISR_CONVT_TRAIN_ROUTE", "kernel")
+
+
+def _convt_train_kernel(n, h, w):
+    return bool(TRAIN_SPLIT and CONVT_TRAIN_ROUTE == "kernel" and _sr().isrConvTranspose3x3S2SplitSupported(64, 64, h, w, h * w, 4 * h * w)
+                and _sr().isrConvTranspose3x3S2DataGradSplitSupported(n, 64, h, w))
+
+
+def conv_transpose_phase_gradient(gy, y=None, act='none', slope=0.01):
+    """The PHASE-MAJOR gradient of a stride-2 transposed convolution's output: G[n, 4 c + 2 a + b, i, j] = gz[n, c, 2i + a, 2j + b] with
+    gz = gy act'(y) by the rule of ``isrActBackward`` (gy where y > 0, gy * slope elsewhere; slope 0 for 'relu') -- that launch followed
+    by ``F.pixel_unshuffle(., 2)``, as ONE element-wise kernel (``isrConvTransposePhaseGradient``) on device tensors; CPU tensors: the
+    definition.  gy, y: [N, C, 2h, 2w]; y may be None with act 'none'."""
+    if act not in ('none', 'relu', 'leaky'):
+        raise ValueError("unknown activation %r" % (act,))
+    if act != 'none' and y is None:
+        raise ValueError("conv_transpose_phase_gradient: the activation's backward needs y")
+    n, c, hh, ww = gy.shape
+    if hh % 2 or ww % 2:
+        raise ValueError("conv_transpose_phase_gradient: even height and width expected")
+    if not gy.is_cuda:
+        gz = gy if act == 'none' else torch.where(y > 0, gy, gy * (0.0 if act == 'relu' else slope))
+        return torch.stack([gz[:, :, a::2, b::2] for a in (0, 1) for b in (0, 1)], dim=2).reshape(n, 4 * c, hh // 2, ww // 2)
+    if gy.dtype != torch.float32:
+        raise TypeError("conv_transpose_phase_gradient (HIP) computes in fp32")
+    gy = gy.contiguous()
+    y = y.contiguous() if act != 'none' else None
+    g = torch.empty((n, 4 * c, hh // 2, ww // 2), dtype=torch.float32, device=gy.device)
+    rc = _sr().isrConvTransposePhaseGradient(_ptr(gy), _ptr(y), _ptr(g), n, c, hh // 2, ww // 2, ACT_CODES[act], float(slope), _stream())
+    if rc != 0:
+        raise RuntimeError("isrConvTransposePhaseGradient failed (%d)" % rc)
+    return g
+
+
+def _convt_data_grad(g, weight):
+    """gx [N, 64, h, w] from the phase-major gradient g [N, 256, h, w] (packed) on ``convt3x3s2_dgrad_split_kernel``.  Inside
+    ``deferred_weight_gradients()`` the launch leaves the maxima of gx in the per-step words, as the split data gradient of
+    ``_train_conv`` does: gx is some layer's gz later on."""
+    lib = _sr()
+    n, _, h, w = g.shape
+    _tally("split", 2.0 * 9 * 64 * 64 * n * h * w)
+    gx = torch.empty((n, 64, h, w), dtype=torch.float32, device=g.device)
+    slot = _gmax_slot(g.device, _GMAX_CONV_WORDS)
+    if slot is not None:
+        lib.isrSetMaxSlots(ctypes.c_void_p(slot), _GMAX_CONV_WORDS)
+    rc = lib.isrConvTranspose3x3S2DataGradSplit(_ptr(g), _ptr(_prepare_convt(weight, "dgrad")), _ptr(gx), n, 64, h, w, _stream())
+    if rc != 0:
+        raise RuntimeError("isrConvTranspose3x3S2DataGradSplit failed (%d)" % rc)
+    if slot is not None:
+        words = lib.isrTakeMaxSlotWords()
+        if words > 0:
+            _gmax_tag(gx, slot, words)
+    return gx
+
+
+def _convt_data_grad_embedded(g, weight, bias):
+    """The same gradient as the data gradient of the zero-embedded 64 -> 256 layer on the convolution's own training kernels."""
+    return _train_conv(g, _convt_embedded(weight, bias)[0], True, None, None, 'none')
+
+
+class _ConvTranspose3x3S2Function(torch.autograd.Function):
+    """y = act(conv_transpose2d(x, w, b, 2, 1, 1)) for 64 -> 64 channels as ONE autograd node on the HIP training kernels: forward
+    ``isrConvTranspose3x3S2ForwardSplitBatch`` (the inference kernel, the whole batch in one launch; packed output, no range word armed:
+    the training rule of ``_train_conv``); backward
+    ``isrConvTransposePhaseGradient`` (the activation's backward, written phase-major), ``isrConvTranspose3x3S2DataGradSplit`` and the
+    weight gradient of (x, G) as a 64 -> 256 layer through ``_weight_grad_or_defer``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, slope):
+        lib = _sr()
+        x = x.contiguous()
+        n, _, h, w = x.shape
+        b = bias.detach().contiguous() if bias is not None else None
+        if _convt_train_kernel(n, h, w):
+            _tally("split", 2.0 * 9 * 64 * 64 * n * h * w)
+            wq = _prepare_convt(weight)
+            y = torch.empty((n, 64, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+            rc = lib.isrConvTranspose3x3S2ForwardSplitBatch(_ptr(x), _ptr(wq), _ptr(b), _ptr(y), n, h, w, ACT_CODES[act], float(slope), _stream())
+            if rc != 0:
+                raise RuntimeError("isrConvTranspose3x3S2ForwardSplitBatch failed (%d)" % rc)
+        elif TRAIN_SPLIT and CONVT_TRAIN_ROUTE == "embedded" and w % 4 == 0 and _split_fits(x, 256, False):
+            _tally("split", 2.0 * 9 * 64 * 256 * n * h * w)
+            we, be = _convt_embedded(weight, bias)
+            y = F.pixel_shuffle(_launch_lp("isrConv3x3ForwardSplit", x, _prepare_split(we), be, None, 256, act, slope, False, packed=True), 2)
+        else:
+            _tally("exact", 2.0 * 9 * 64 * 256 * n * h * w)
+            y = _conv_transpose_exact(x, weight, bias, act, slope)
+        ctx.act, ctx.slope = act, slope
+        ctx.has_bias = bias is not None
+        ctx.bias_any = bias
+        ctx.bias = bias if (bias is not None and bias.requires_grad) else None
+        ctx.weight = weight
+        ctx.save_for_backward(x, y if act != 'none' else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y = ctx.saved_tensors
+        weight = ctx.weight
+        n, _, h, w = x.shape
+        g = conv_transpose_phase_gradient(gy, y, ctx.act, ctx.slope)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            if _convt_train_kernel(n, h, w):
+                gx = _convt_data_grad(g, weight)
+            else:
+                gx = _convt_data_grad_embedded(g, weight, ctx.bias_any)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw, gb = _weight_grad_or_defer(weight, ctx.bias, ctx.has_bias, x, g, convt=True)
+        return gx, gw, gb, None, None
+
+
 def conv_transpose3x3_s2(x, weight, bias=None, act='none', slope=0.01):
     """y = act(conv_transpose2d(x, w, bias, stride=2, padding=1, output_padding=1)): x [N, Cin, h, w], weight [Cin, Cout, 3, 3] (the
     ``nn.ConvTranspose2d`` layout) -> [N, Cout, 2h, 2w].  TecoGAN's two upsampling layers (64 -> 64).
@@ -1516,8 +1683,13 @@ def conv_transpose3x3_s2(x, weight, bias=None, act='none', slope=0.01):
       its output armed with a range key like ``conv3x3_split``'s.  With the input's range key hot, ``SPLIT_F16`` off or a shape the
       kernel does not take (channels other than 64, more than 2 GiB): the exact fp32 route -- the four phases as zero-padded 3x3
       taps of a [4 Cout, Cin, 3, 3] weight on the exact ``conv3x3`` kernel, then ``F.pixel_shuffle``.
-    * under autograd: PyTorch's own transposed convolution (a warning says so, once).  TRAINING a TecoGAN is not on the HIP path -- the
-      transposed convolution has no backward kernels here -- and no GPU test runs this route."""
+    * under autograd, device fp32 64 -> 64: ``_ConvTranspose3x3S2Function`` -- forward on the split kernel (packed output; the exact
+      embedded route with ``TRAIN_SPLIT`` off or a shape the kernel does not take), backward as the phase-major gradient
+      (``isrConvTransposePhaseGradient``), the dedicated split-operand data gradient (``isrConvTranspose3x3S2DataGradSplit``, only when
+      the input needs a gradient) and the weight gradient of (x, G) as a 64 -> 256 layer on the convolution's segment kernels, deferred
+      inside ``deferred_weight_gradients()`` like every other layer's.  Under ``TRAIN_BF16`` these layers STAY on the split kernels
+      (there are no bf16 forms of them).
+    * under autograd, other channel counts: PyTorch's own transposed convolution (a warning says so, once)."""
     if act not in ('none', 'relu', 'leaky'):
         raise ValueError("unknown activation %r" % (act,))
     if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != weight.shape[0]:
@@ -1527,9 +1699,11 @@ def conv_transpose3x3_s2(x, weight, bias=None, act='none', slope=0.01):
     if x.dtype != torch.float32 or weight.dtype != torch.float32:
         raise TypeError("conv_transpose3x3_s2 (HIP) computes in fp32")
     needs_grad = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
+    if needs_grad and tuple(weight.shape[:2]) == (64, 64) and CONVT_TRAIN_ROUTE != "torch":
+        return _ConvTranspose3x3S2Function.apply(x, weight, bias, act, slope)
     if needs_grad:
-        _warn_once("convt_autograd", "conv_transpose3x3_s2: under autograd the transposed convolution runs on PyTorch's own kernels "
-                   "(training a TecoGAN is not on the HIP path)")
+        _warn_once("convt_autograd", "conv_transpose3x3_s2: under autograd this transposed convolution runs on PyTorch's own kernels "
+                   "(the HIP training kernels take 64 -> 64 channels)")
         return _act_cpu(F.conv_transpose2d(x, weight, bias, stride=2, padding=1, output_padding=1), act, slope)
     hot_in = range_is_hot(getattr(x, '_isr_range_key', None), x.device)
     if SPLIT_F16 and not hot_in and _convt_fits(x, weight):
