@@ -571,6 +571,39 @@ int isrMetricsAbsDiffHistogram(const float* a, long long aRow, long long aPlane,
                                const double* blend, long long blendRow, int C, int H, int W, double scale, int bins, const double* edges,
                                long long* counts, void* stream);
 
+/* The pieces of the RCAN generator (models/rcan.py) that are not convolutions (csrc/sr_attention.hip).  Tensors are fp32 with packed rows,
+ * addressed as base + n * image + c * plane + y * W + x (strides in floats, plane >= H W: the pad behind a plane is never read); C = 64
+ * channels with R = 4 reduced channels, one image below 2 GiB, N <= 65535: anything else returns -3 (the ...Supported predicates say so
+ * beforehand).  Returns: 0, -1 bad arguments, -2 launch failure, -3 unsupported.  16-byte accesses where base addresses and strides are
+ * multiples of 16 bytes, a per-element path otherwise.
+ *
+ * Channel attention of a residual block, y = x + t * s[c] with s = sigmoid(Wu leaky(Wd mean_hw(t) + bd) + bu), in two launches:
+ *   isrChannelPool: workspace[n][c][s] (double, S = isrChannelPoolSlabs(N, H, W) slabs per plane; S fills the chip at 480 x 270 and is 1
+ *     for small planes) = the sum of slab s of plane (n, c) of t, accumulated in fp64 in a fixed order: the same bits on every run, no
+ *     floating-point atomics.  isrChannelPoolMean: mean[n][c] = (float)(sum of the S partials in index order / (H W)) -- the value
+ *     the gate below forms itself.
+ *   isrChannelGateScaleAdd: every workgroup sums the S partials of its image in index order, forms the fp32 mean z[64], computes
+ *     a[j] = fmaf-chain over c of Wd[j][c] z[c] starting from bd[j]; g = a > 0 ? a : a * slope; u = fmaf-chain over j of Wu[c][j] g[j]
+ *     starting from bu[c]; s = 1 / (1 + expf(-u)), and stores y = x + t * s as a separately rounded multiply and add (given s, the bits of
+ *     `x + t * s` in PyTorch).  wDown [4][64], bDown [4], wUp [64][4], bUp [64] as nn.Linear stores them.  `gate`: [N][64] receives s, or
+ *     NULL.  Range guard: a launch armed by isrSetRangeFlag reports the largest |y| it stores, one atomic per wave.
+ * The tail, out [N][Cout <= 8][4h][4w] = conv3x3(pixel_shuffle(f [N][64][h][w], 4), weight [Cout][4][3][3], zero padding 1) + bias
+ * (NULL: none), clamped to [0, 1] if `clamp`, in ONE launch (isrShuffleTailColour): channel 16 c + 4 i + j of low-resolution pixel (y, x)
+ * is channel c at (4 y + i, 4 x + j); the low-resolution tile and its one-pixel halo are staged in LDS, the four-channel high-resolution
+ * tensor never exists in memory.  Per output value one fp32 fmaf chain starting from the bias, over (ci, ky, kx) in this nesting, zeros
+ * outside the image: the value does not depend on where tile borders fall. */
+int isrChannelPoolSlabs(int N, int H, int W);
+int isrChannelPoolSupported(int N, int C, int H, int W, long long plane, long long image);       /* one tensor with these strides */
+int isrChannelGateScaleAddSupported(int N, int C, int R, int H, int W, long long plane, long long image);       /* each of x, t, y */
+int isrChannelPool(const float* t, long long tPlane, long long tImage, int N, int C, int H, int W, int S, double* workspace, void* stream);
+int isrChannelPoolMean(const double* workspace, int N, int C, int H, int W, int S, float* mean, void* stream);
+int isrChannelGateScaleAdd(const float* x, const float* t, float* y, long long xPlane, long long xImage, long long tPlane, long long tImage,
+                           long long yPlane, long long yImage, const double* workspace, int S, const float* wDown, const float* bDown,
+                           const float* wUp, const float* bUp, float slope, float* gate, int N, int C, int R, int H, int W, void* stream);
+int isrShuffleTailColourSupported(int N, int C, int Cout, int h, int w, long long fPlane, long long fImage, long long outPlane, long long outImage);
+int isrShuffleTailColour(const float* f, long long fPlane, long long fImage, const float* weight, const float* bias, float* out,
+                         long long outPlane, long long outImage, int N, int C, int Cout, int h, int w, int clamp, void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

@@ -185,6 +185,16 @@ def _bind(lib):
         lib.isrConvTransposeDataGradPrepare.argtypes = [vp, vp, vp]; lib.isrConvTransposeDataGradPrepare.restype = ci
         lib.isrConvTranspose3x3S2DataGradSplitSupported.argtypes = [ci, ci, ci, ci]; lib.isrConvTranspose3x3S2DataGradSplitSupported.restype = ci
         lib.isrConvTranspose3x3S2DataGradSplit.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]; lib.isrConvTranspose3x3S2DataGradSplit.restype = ci
+    if hasattr(lib, "isrChannelGateScaleAdd"):                  # (likewise: RCAN's channel attention and pixel-shuffle tail, csrc/sr_attention.hip)
+        lib.isrChannelPoolSlabs.argtypes = [ci, ci, ci]; lib.isrChannelPoolSlabs.restype = ci
+        lib.isrChannelPoolSupported.argtypes = [ci, ci, ci, ci, ll, ll]; lib.isrChannelPoolSupported.restype = ci
+        lib.isrChannelGateScaleAddSupported.argtypes = [ci, ci, ci, ci, ci, ll, ll]; lib.isrChannelGateScaleAddSupported.restype = ci
+        lib.isrChannelPool.argtypes = [vp, ll, ll, ci, ci, ci, ci, ci, vp, vp]; lib.isrChannelPool.restype = ci
+        lib.isrChannelPoolMean.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp]; lib.isrChannelPoolMean.restype = ci
+        lib.isrChannelGateScaleAdd.argtypes = [vp, vp, vp, ll, ll, ll, ll, ll, ll, vp, ci, vp, vp, vp, vp, cf, vp, ci, ci, ci, ci, ci, vp]
+        lib.isrChannelGateScaleAdd.restype = ci
+        lib.isrShuffleTailColourSupported.argtypes = [ci, ci, ci, ci, ci, ll, ll, ll, ll]; lib.isrShuffleTailColourSupported.restype = ci
+        lib.isrShuffleTailColour.argtypes = [vp, ll, ll, vp, vp, vp, ll, ll, ci, ci, ci, ci, ci, ci, vp]; lib.isrShuffleTailColour.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -380,7 +390,9 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  33: "conv3x3_split_tail_colour_kernel", 34: "tail_finish_colour_kernel", 35: "assemble_input_colour_kernel",
                  36: "finish_frame_colour_kernel",
                  # the transposed convolution of the TecoGAN generator (csrc/sr_conv_transpose.hip)
-                 37: "convt3x3s2_split_kernel", 38: "convt3x3s2_dgrad_split_kernel"}
+                 37: "convt3x3s2_split_kernel", 38: "convt3x3s2_dgrad_split_kernel",
+                 # RCAN's channel attention and pixel-shuffle tail (csrc/sr_attention.hip)
+                 39: "channel_pool_kernel", 40: "gate_scale_add_kernel", 41: "shuffle_tail_kernel"}
 
 
 def debug_switches():
@@ -2446,8 +2458,167 @@ def tail_conv_finish_colour(features, weight6, bias6, weight8, bias8, net_input,
     return out
 
 
+# ---- RCAN: channel attention and the pixel-shuffle tail (csrc/sr_attention.hip) -------------------------------------------------------------
+# The three pieces of models/rcan.py that are not convolutions.  Each function's CPU branch is its DEFINITION in plain torch (as
+# ``conv3x3``'s is); a device tensor without autograd takes the HIP kernels where ``*_supported`` says so and the same torch composite
+# (with a warning, once) where the kernels refuse; under autograd each IS the torch composite (there are no backward kernels for them).
+ATTENTION_CHANNELS = 64
+ATTENTION_REDUCED = 4
+# False: the three ops run their torch composite on the device without a word (tools/bench_rcan.py's comparison: the same network with
+# its non-convolution pieces on PyTorch-ROCm's operators).  A MEASUREMENT switch: the composite's output is not watched by the range guard.
+ATTENTION_KERNELS = True
+
+
+def _any_requires_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _strides_of(t):
+    """(plane, image) strides ``_plane_strides`` will hand to a kernel for ``t`` -- without copying anything."""
+    n, c, h, w = t.shape
+    if t.stride(3) == 1 and t.stride(2) == w and t.stride(1) >= h * w and (n == 1 or t.stride(0) >= c * t.stride(1)):
+        return t.stride(1), t.stride(0) if n > 1 else c * t.stride(1)
+    return h * w, c * h * w
+
+
+def channel_pool_supported(t):
+    """``isrChannelPool`` takes this tensor: fp32 [N, 64, H, W] on the device, one image below 2 GiB."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0):
+        return False
+    n, c, h, w = t.shape
+    plane, image = _strides_of(t)
+    return bool(_sr().isrChannelPoolSupported(n, c, h, w, plane, image))
+
+
+def _channel_pool_cpu(t):
+    n, c, h, w = t.shape
+    return torch.mean(t.reshape(n, c, h * w), dim=2)
+
+
+def _pool_partials(t):
+    """-> (t with packed rows, plane stride, image stride, S, workspace double [N][64][S]) after ``isrChannelPool``."""
+    lib = _sr()
+    t, tp, ti = _plane_strides(t)
+    n, c, h, w = t.shape
+    slabs = lib.isrChannelPoolSlabs(n, h, w)
+    ws = torch.empty(n * c * slabs, dtype=torch.float64, device=t.device)
+    rc = lib.isrChannelPool(_ptr(t), tp, ti, n, c, h, w, slabs, _ptr(ws), _stream())
+    if rc != 0:
+        raise RuntimeError("isrChannelPool failed (%d)" % rc)
+    return t, tp, ti, slabs, ws
+
+
+def channel_pool(t):
+    """[N, 64, H, W] -> the [N, 64] mean over H x W (the squeeze of the channel attention).  HIP: slab sums in fp64 in a fixed order
+    (``isrChannelPool``), summed in index order and rounded to fp32 once (``isrChannelPoolMean``): two calls give the same bits."""
+    if not t.is_cuda or _any_requires_grad(t) or not ATTENTION_KERNELS:
+        return _channel_pool_cpu(t)
+    if not channel_pool_supported(t):
+        _warn_once("channel_pool", "channel_pool: %s is not what the HIP kernel takes; torch.mean runs instead" % (tuple(t.shape),))
+        return _channel_pool_cpu(t)
+    with torch.no_grad():
+        t, _, _, slabs, ws = _pool_partials(t)
+        n, c, h, w = t.shape
+        mean = torch.empty((n, c), dtype=torch.float32, device=t.device)
+        rc = _sr().isrChannelPoolMean(_ptr(ws), n, c, h, w, slabs, _ptr(mean), _stream())
+        if rc != 0:
+            raise RuntimeError("isrChannelPoolMean failed (%d)" % rc)
+        return mean
+
+
+def channel_attention_supported(x, t, w_down, w_up):
+    """The two attention launches take these operands: x, t fp32 [N, 64, H, W] on one device, a 64 -> 4 -> 64 perceptron."""
+    if not (channel_pool_supported(t) and channel_pool_supported(x) and x.shape == t.shape and x.device == t.device):
+        return False
+    n, c, h, w = x.shape
+    if not all(_sr().isrChannelGateScaleAddSupported(n, c, w_down.shape[0], h, w, *_strides_of(v)) for v in (x, t)):
+        return False
+    return tuple(w_down.shape) == (ATTENTION_REDUCED, ATTENTION_CHANNELS) and tuple(w_up.shape) == (ATTENTION_CHANNELS, ATTENTION_REDUCED) \
+        and w_down.dtype == torch.float32 and w_up.dtype == torch.float32 and w_down.is_cuda and w_up.is_cuda
+
+
+def _channel_attention_cpu(x, t, w_down, b_down, w_up, b_up, slope, return_gate):
+    z = _channel_pool_cpu(t)
+    s = torch.sigmoid(F.linear(F.leaky_relu(F.linear(z, w_down, b_down), slope), w_up, b_up))
+    y = x + t * s[:, :, None, None]
+    return (y, s) if return_gate else y
+
+
+def channel_attention_residual(x, t, w_down, b_down, w_up, b_up, slope=0.01, return_gate=False, range_key=None):
+    """A residual channel-attention block's ``x + t * s``: s [N, 64] = sigmoid(W_up leaky_relu(W_down mean_hw(t) + b_down) + b_up)
+    (``nn.Linear`` layouts).  HIP: two launches -- ``isrChannelPool`` and ``isrChannelGateScaleAdd`` (the perceptron recomputed per
+    workgroup in a fixed fmaf order; given s, y is bitwise ``x + t * s[:, :, None, None]``).  ``return_gate``: -> (y, s).
+    ``range_key``: the range guard's word this launch reports the largest |y| to (``_arm_range``; models/rcan.py hands in the word of
+    the block's second convolution, so that a block costs one word): y is tagged with it, and a hot y sends its consumer to the exact
+    kernels through ``conv3x3``'s routing; without a key y counts as of unknown range only if x or t do."""
+    if not x.is_cuda or _any_requires_grad(x, t, w_down, b_down, w_up, b_up) or not ATTENTION_KERNELS:
+        return _channel_attention_cpu(x, t, w_down, b_down, w_up, b_up, slope, return_gate)
+    if not channel_attention_supported(x, t, w_down, w_up):
+        _warn_once("channel_attention", "channel_attention_residual: %s is not what the HIP kernels take; PyTorch operators run instead"
+                   % (tuple(x.shape),))
+        out = _channel_attention_cpu(x, t, w_down, b_down, w_up, b_up, slope, return_gate)
+        (out[0] if return_gate else out)._isr_range_key = HOT          # nobody watched its range
+        return out
+    lib = _sr()
+    with torch.no_grad():
+        unknown = HOT in (getattr(x, '_isr_range_key', None), getattr(t, '_isr_range_key', None))
+        t, tp, ti, slabs, ws = _pool_partials(t)
+        x, xp, xi = _plane_strides(x)
+        n, c, h, w = x.shape
+        y = empty_planes(n, c, h, w, x.device)
+        gate = torch.empty((n, c), dtype=torch.float32, device=x.device) if return_gate else None
+        wd, bd, wu, bu = (p.detach().contiguous() for p in (w_down, b_down, w_up, b_up))
+        key = _arm_range(range_key, x.device) if range_key is not None else None
+        rc = lib.isrChannelGateScaleAdd(_ptr(x), _ptr(t), _ptr(y), xp, xi, tp, ti, y.stride(1), c * y.stride(1), _ptr(ws), slabs,
+                                        _ptr(wd), _ptr(bd), _ptr(wu), _ptr(bu), float(slope), _ptr(gate), n, c, ATTENTION_REDUCED, h, w, _stream())
+        if rc != 0:
+            raise RuntimeError("isrChannelGateScaleAdd failed (%d)" % rc)
+        y._isr_range_key = HOT if unknown else key
+        return (y, gate) if return_gate else y
+
+
+def pixel_shuffle4_conv_supported(f, weight):
+    """``isrShuffleTailColour`` takes these operands: f fp32 [N, 64, h, w] on the device, weight [Cout <= 8, 4, 3, 3]."""
+    if not (torch.is_tensor(f) and f.is_cuda and f.dtype == torch.float32 and f.dim() == 4 and f.numel() > 0 and weight.is_cuda
+            and weight.dtype == torch.float32 and weight.dim() == 4 and tuple(weight.shape[1:]) == (4, 3, 3)):
+        return False
+    n, c, h, w = f.shape
+    plane, image = _strides_of(f)
+    cout = weight.shape[0]
+    return bool(_sr().isrShuffleTailColourSupported(n, c, cout, h, w, plane, image, 16 * h * w, cout * 16 * h * w))
+
+
+def _pixel_shuffle4_conv_cpu(f, weight, bias, clamp):
+    out = F.conv2d(F.pixel_shuffle(f, 4), weight, bias, padding=1)
+    return torch.clamp(out, 0, 1) if clamp else out
+
+
+def pixel_shuffle4_conv(f, weight, bias, clamp=False):
+    """RCAN's tail: conv3x3(pixel_shuffle(f [N, 64, h, w], 4), weight [Cout, 4, 3, 3], padding 1) + bias -> [N, Cout, 4h, 4w], clamped
+    to [0, 1] with ``clamp``.  HIP: one launch (``isrShuffleTailColour``), the shuffled four-channel tensor stays in LDS; per value an
+    fp32 fmaf chain over (ci, ky, kx) starting from the bias.  Under autograd: ``F.pixel_shuffle`` and ``F.conv2d``."""
+    if not f.is_cuda or _any_requires_grad(f, weight, bias) or not ATTENTION_KERNELS:
+        return _pixel_shuffle4_conv_cpu(f, weight, bias, clamp)
+    if not pixel_shuffle4_conv_supported(f, weight):
+        _warn_once("pixel_shuffle4_conv", "pixel_shuffle4_conv: %s with weight %s is not what the HIP kernel takes; PyTorch operators run instead"
+                   % (tuple(f.shape), tuple(weight.shape)))
+        return _pixel_shuffle4_conv_cpu(f, weight, bias, clamp)
+    with torch.no_grad():
+        f, fp, fi = _plane_strides(f)
+        n, c, h, w = f.shape
+        cout = weight.shape[0]
+        out = torch.empty((n, cout, 4 * h, 4 * w), dtype=torch.float32, device=f.device)
+        wt = weight.detach().contiguous()
+        b = bias.detach().contiguous() if bias is not None else None
+        rc = _sr().isrShuffleTailColour(_ptr(f), fp, fi, _ptr(wt), _ptr(b), _ptr(out), 16 * h * w, cout * 16 * h * w, n, c, cout, h, w,
+                                        1 if clamp else 0, _stream())
+        if rc != 0:
+            raise RuntimeError("isrShuffleTailColour failed (%d)" % rc)
+        return out
+
+
 # ---- the viewer's display stage (viewer.py) --------------------------------------------------------------------------------------------
-DISPLAY_VIEWS = {"color": 0, "mask": 1, "normal": 2, "depth": 3, "ao": 4, "flow": 5}       # ISR_VIEW_*
+DISPLAY_VIEWS ={"color": 0, "mask": 1, "normal": 2, "depth": 3, "ao": 4, "flow": 5}       # ISR_VIEW_*
 
 
 def display_supported(gbuffer_hwc, rgb, raw=None):

@@ -14,6 +14,7 @@ import torch
 
 from . import ops
 from .inference.flowfill import fill_flow
+from .models.rcan import RCAN
 from .models.tecogan import TecoGAN
 from .utils import ScreenSpaceShading
 from .volumes import fmt3
@@ -73,8 +74,14 @@ def run_network_colour(model, x, after_trunk=None, prefetch_point="trunk"):
     where ``ops.packed_supported``) -> the three-channel fused tail (``ops.tail_conv_finish_colour`` where ``ops.tail_supported``);
     with a layer on the range guard's exact route, the per-layer kernels and the small-Cout last layer with the colour finishing in
     its epilogue.  A colour TecoGAN: ``forward_features`` (per-layer kernels, the transposed convolutions on
-    ``ops.conv_transpose3x3_s2``), then ``ops.finish_frame_colour``; ``x`` is the fp32 input of ``ops.assemble_input_colour``."""
+    ``ops.conv_transpose3x3_s2``), then ``ops.finish_frame_colour``; ``x`` is the fp32 input of ``ops.assemble_input_colour``.  A colour
+    RCAN: ``forward_features`` (per-layer kernels, two attention launches per block), then ``ops.pixel_shuffle4_conv`` with the clamp in
+    its epilogue -- there is no reconstruction to add."""
     net = model.model
+    if isinstance(net, RCAN):
+        # a colour RCAN (fused_path_ok): the prediction IS the clamped output of the tail (rcan.py:120), one launch behind net.rir
+        post = net.net['post']
+        return ops.pixel_shuffle4_conv(net.forward_features(x, after_trunk=after_trunk), post.weight, post.bias, clamp=True)
     if isinstance(net, TecoGAN):
         # a colour TecoGAN (fused_path_ok): its own layers -- the last one carries a LeakyReLU, so no finishing is folded into it --
         # then reconstruction + clamp as one launch
@@ -138,8 +145,13 @@ def is_colour(model):
 
 def fused_path_ok(model, upscale=4):
     """The fused frame kernels take this network: 4x, residual reconstruction over the five input channels -- or, a colour model, over
-    [0, 1, 2] with three outputs, bilinear upsampling and no batch norm (EnhanceNet) / a last convolution 64 -> 3 (TecoGAN)."""
+    [0, 1, 2] with three outputs, bilinear upsampling and no batch norm (EnhanceNet) / a last convolution 64 -> 3 (TecoGAN); a colour
+    RCAN (no reconstruction type to ask for) with mask [0, 1, 2] and a last convolution 4 -> 3."""
     net = model.model
+    if isinstance(net, RCAN):
+        post = net.net['post']
+        return upscale == 4 and is_colour(model) and list(net.channel_mask) == [0, 1, 2] \
+            and (post.in_channels, post.out_channels) == (4, 3) and model.input_channels - 48 in ops.COLOUR_VARIANTS
     if upscale != 4 or getattr(net, 'recon_type', None) != 'residual' or getattr(net, 'channel_mask', None) is None:
         return False
     if isinstance(net, TecoGAN):
