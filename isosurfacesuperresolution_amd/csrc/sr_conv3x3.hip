@@ -30,6 +30,7 @@
 #include "sr_finish.h"
 #include "sr_profile.h"
 #include "sr_act.h"
+#include "sr_split_scale.h"
 
 namespace {
 
@@ -1581,24 +1582,10 @@ __global__ __launch_bounds__(256) void wgrad_absmax_kernel(const AbsMaxParams p,
 }
 __global__ __launch_bounds__(256) void wgrad_scale_kernel(const float* __restrict__ partial, int n, float* __restrict__ scale)
 {
-    __shared__ float red[256];
     float mx = 0.0f;
-    for (int i = threadIdx.x; i < n; i += 256) mx = fmaxf(mx, partial[i]);
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        int S = 0;
-        if (red[0] > 0.0f && red[0] < 3.0e38f) {
-            S = 13 - ilogbf(red[0]);
-            S = S < -100 ? -100 : (S > 100 ? 100 : S);
-        }
-        scale[0] = ldexpf(1.0f, S);
-        scale[1] = ldexpf(1.0f, -S);
-    }
+    for (int i = threadIdx.x; i < n; i += 256) mx = isr_max(mx, partial[i]);
+    mx = isr_block_max(mx);
+    if (threadIdx.x == 0) isr_scale_pair(isr_scale_exponent(mx), scale);
 }
 
 // ... the same pair from maxima the PRODUCERS of the gz tensors left behind (bit patterns of max |gz|, one word per tensor: the
@@ -1606,27 +1593,13 @@ __global__ __launch_bounds__(256) void wgrad_scale_kernel(const float* __restric
 struct MaxFlagParams { const unsigned* f[WG_MAX_SEG]; int segments, words; };
 __global__ __launch_bounds__(1024) void wgrad_scale_flags_kernel(const MaxFlagParams p, float* __restrict__ scale)
 {
-    __shared__ unsigned red[16];
     unsigned m = 0u;
     for (int i = threadIdx.x; i < p.words; i += 1024) {
 #pragma unroll 8
-        for (int s = 0; s < p.segments; ++s) { const unsigned t = p.f[s][i]; m = t > m ? t : m; }
+        for (int s = 0; s < p.segments; ++s) m = isr_max(m, p.f[s][i]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)m, o, 64); m = t > m ? t : m; }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 16; ++k) m = red[k] > m ? red[k] : m;
-        const float mx = __builtin_bit_cast(float, m);
-        int S = 0;
-        if (mx > 0.0f && mx < 3.0e38f) {
-            S = 13 - ilogbf(mx);
-            S = S < -100 ? -100 : (S > 100 ? 100 : S);
-        }
-        scale[0] = ldexpf(1.0f, S);
-        scale[1] = ldexpf(1.0f, -S);
-    }
+    m = isr_block_max(m);
+    if (threadIdx.x == 0) isr_scale_pair(isr_scale_exponent(__builtin_bit_cast(float, m)), scale);
 }
 
 // dw[co][ci][tap] = sum over the G slabs, in a fixed order (bitwise reproducible run to run).  A workgroup owns 64

@@ -18,6 +18,7 @@
 #include "sr_diag.h"
 #include <cstdlib>
 #include "sr_split_common.h"
+#include "sr_split_scale.h"
 
 namespace {
 
@@ -719,29 +720,11 @@ template <int CO>
 __global__ __launch_bounds__(256) void tail_prepare_kernel(const float* __restrict__ w8, u32x4* __restrict__ wz)
 {
     using TSH = TailShape<CO>;
-    __shared__ float red[256];
     float m = 0.0f;
-    for (int i = threadIdx.x; i < CO * 64 * 9; i += 256) m = fmaxf(m, fabsf(w8[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    int S = 0;
-    const float mx = red[0];
-    if (mx > 0.0f && mx < 3.0e38f) {
-        S = 13 - ilogbf(mx);
-        S = S < -100 ? -100 : (S > 100 ? 100 : S);
-    }
+    for (int i = threadIdx.x; i < CO * 64 * 9; i += 256) m = isr_max(m, fabsf(w8[i]));
+    const int S = isr_scale_exponent(isr_block_max(m));
     const float scale = ldexpf(1.0f, S);
-    if (threadIdx.x == 0) {
-        u32x4 hdr;
-        hdr.x = __builtin_bit_cast(unsigned, scale);
-        hdr.y = __builtin_bit_cast(unsigned, ldexpf(1.0f, -S));
-        hdr.z = (unsigned)S; hdr.w = 0u;
-        wz[0] = hdr;
-    }
+    if (threadIdx.x == 0) isr_scale_header(S, wz);
     for (int u = threadIdx.x; u < 4 * 2 * 64; u += 256) {                     // (q, h, m)
         const int mrow = u & 63, hh = (u >> 6) & 1, q = u >> 7;
         const int dxr = mrow / TSH::GROUPS, gr = mrow - dxr * TSH::GROUPS;    // row [dx][dy][c] (tail_zrow)

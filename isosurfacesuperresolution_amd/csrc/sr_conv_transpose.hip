@@ -10,7 +10,7 @@
 // the missing neighbour outside the image).
 //
 // Arithmetic: the split-operand scheme of sr_conv_split.hip (sr_split_common.h): activations as (hi, lo' = lo 2^11) fp16 pairs made on
-// the way into LDS, weights as scaled (hi, lo) pairs prepared once, three v_mfma_f32_32x32x16_f16 per product, fp32 accumulation.
+// the way into LDS, weights as scaled (hi, lo) pairs prepared once (sr_split_prepare.hip), three v_mfma_f32_32x32x16_f16 per product, fp32 accumulation.
 //
 // Structure: workgroup = 4 x 32 low-resolution pixels (8 x 64 output pixels) x 64 output channels, 4 waves, wave w owns low-resolution
 // row w: FOUR accumulator sets (the phases) x 2 channel blocks = 128 registers.  The input is staged in chunks of 32 channels as
@@ -39,7 +39,6 @@ constexpr int CT_PUNITS = 2 * CT_PART;
 constexpr int CT_LDS_BYTES = (CT_PUNITS + S_WUNITS) * 16;                    // 21 120 + 36 864 = 57 984: two workgroups per CU
 constexpr int CT_C = 64;                                                     // channels in and out
 constexpr int CT_KSTEPS = CT_C / 16;
-constexpr long long CT_WBYTES = 16 + (long long)9 * CT_KSTEPS * 4 * CT_C * 16;    // header + [tap][k-step][hi | lo][lane half][64 couts] units
 
 struct ConvTParams {
     const float* x; const u32x4* wq; const float* bias; float* y;
@@ -407,56 +406,6 @@ __global__ __launch_bounds__(S_THREADS, 2) void convt3x3s2_dgrad_split_kernel(co
     isr_range_note(p.absmax, mag);
 }
 
-// header unit of the prepared weights, as isrConvSplitPrepare's: { 2^S, 2^-S, S (int), 0 } with max |w| 2^S in [2^13, 2^14)
-__global__ __launch_bounds__(1024) void convt_scale_kernel(const float* __restrict__ w, int count, u32x4* __restrict__ wq)
-{
-    __shared__ float red[1024];
-    float m = 0.0f;
-    for (int i = threadIdx.x; i < count; i += 1024) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        int S = 0;
-        const float mx = red[0];
-        if (mx > 0.0f && mx < 3.0e38f) {
-            S = 13 - ilogbf(mx);
-            S = S < -100 ? -100 : (S > 100 ? 100 : S);
-        }
-        u32x4 hdr;
-        hdr.x = __builtin_bit_cast(unsigned, ldexpf(1.0f, S));
-        hdr.y = __builtin_bit_cast(unsigned, ldexpf(1.0f, -S));
-        hdr.z = (unsigned)S; hdr.w = 0u;
-        wq[0] = hdr;
-    }
-}
-
-// w[ci][co][ky][kx] fp32 (the ConvTranspose2d layout) -> wq[1 + ((((tap * 4 + k-step) * 2 + part) * 2 + lane half h) * 64 + cout)][8 x fp16];
-// element e of (k-step s, half h) is input channel 16 s + 8 h + e; part 0 = hi, 1 = lo of w 2^S.  No flip: tap = 3 ky + kx as stored.
-// DGRAD: the data gradient's image -- the same layout with the roles swapped: the 64 rows are ci, element e is co = 16 s + 8 h + e.
-template <bool DGRAD>
-__global__ __launch_bounds__(256) void convt_prepare_kernel(const float* __restrict__ w, u32x4* __restrict__ wq)
-{
-    const float scale = reinterpret_cast<const float*>(wq)[0];
-    const int u = blockIdx.x * 256 + threadIdx.x;                            // (tap, k-step, half, cout)
-    if (u >= 9 * CT_KSTEPS * 2 * CT_C) return;
-    const int co = u % CT_C, h = (u / CT_C) & 1, s = (u / (CT_C * 2)) % CT_KSTEPS, tap = u / (CT_C * 2 * CT_KSTEPS);
-    f16x8 qh, ql;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int ci = 16 * s + 8 * h + e;
-        _Float16 a, b;
-        split16(w[(DGRAD ? (size_t)co * CT_C + ci : (size_t)ci * CT_C + co) * 9 + tap] * scale, a, b);
-        qh[e] = a; ql[e] = b;
-    }
-    const size_t base = 1 + (size_t)(((tap * CT_KSTEPS + s) * 2 + 0) * 2 + h) * CT_C + co;
-    wq[base] = __builtin_bit_cast(u32x4, qh);
-    wq[base + (size_t)2 * CT_C] = __builtin_bit_cast(u32x4, ql);
-}
-
 bool convt_supported(int Cin, int Cout, int h, int w, long long xPlane, long long yPlane)
 {
     if (Cin != CT_C || Cout != CT_C || h <= 0 || w <= 0 || h > 16384 || w > 16384) return false;
@@ -477,26 +426,6 @@ bool convt_dgrad_supported(int N, int C, int h, int w)
 } // namespace
 
 extern "C" {
-
-long long isrConvTransposeSplitWeightBytes(void) { return CT_WBYTES; }
-
-int isrConvTransposeSplitPrepare(const float* w, void* wq, void* stream)
-{
-    if (!w || !wq) return -1;
-    hipLaunchKernelGGL(convt_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, CT_C * CT_C * 9, (u32x4*)wq);
-    hipLaunchKernelGGL(convt_prepare_kernel<false>, dim3((9 * CT_KSTEPS * 2 * CT_C + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (u32x4*)wq);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-long long isrConvTransposeDataGradWeightBytes(void) { return CT_WBYTES; }
-
-int isrConvTransposeDataGradPrepare(const float* w, void* wq, void* stream)
-{
-    if (!w || !wq) return -1;
-    hipLaunchKernelGGL(convt_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, CT_C * CT_C * 9, (u32x4*)wq);
-    hipLaunchKernelGGL(convt_prepare_kernel<true>, dim3((9 * CT_KSTEPS * 2 * CT_C + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, (u32x4*)wq);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
 
 int isrConvTranspose3x3S2DataGradSplitSupported(int N, int C, int h, int w)
 {

@@ -303,6 +303,16 @@ class _WeightImages:
                 del self.entries[k]
         self.entries[key] = (weakref.ref(tensors[0]), self._stamp(tensors), image, _images_epoch)
 
+    def get(self, key, tensors, build, what):
+        """The cached image, or the one ``build()`` makes now: it returns (image, return code of the library call ``what``)."""
+        image = self.lookup(key, tensors)
+        if image is None:
+            image, rc = build()
+            if rc != 0:
+                raise RuntimeError("%s failed (%d)" % (what, rc))
+            self.store(key, tensors, image)
+        return image
+
     def clear(self):
         self.entries.clear()
 
@@ -353,22 +363,13 @@ def spin_kernel_forms():
 def prepare_weights(weight, transpose_flip=False):
     """PyTorch [Cout,Cin,3,3] -> kernel layout [9][cinPad][coutPad] (device tensor)."""
     lib = _sr()
-    cout, cin = weight.shape[0], weight.shape[1]
-    key = (id(weight), bool(transpose_flip))
-    wp = _wcache.lookup(key, (weight,))
-    if wp is not None:
-        return wp
-    w = weight.detach().contiguous()
-    if transpose_flip:
-        cin_pad, cout_pad = lib.isrConvCinPad(cout), lib.isrConvCoutPad(cin)
-    else:
-        cin_pad, cout_pad = lib.isrConvCinPad(cin), lib.isrConvCoutPad(cout)
-    wp = torch.empty(9 * cin_pad * cout_pad, dtype=torch.float32, device=weight.device)
-    rc = lib.isrConvPrepareWeights(_ptr(w), _ptr(wp), cout, cin, 1 if transpose_flip else 0, _stream())
-    if rc != 0:
-        raise RuntimeError("isrConvPrepareWeights failed (%d)" % rc)
-    _wcache.store(key, (weight,), wp)
-    return wp
+
+    def build():
+        cout, cin = weight.shape[0], weight.shape[1]
+        rows, k = (cin, cout) if transpose_flip else (cout, cin)
+        wp = torch.empty(9 * lib.isrConvCinPad(k) * lib.isrConvCoutPad(rows), dtype=torch.float32, device=weight.device)
+        return wp, lib.isrConvPrepareWeights(_ptr(weight.detach().contiguous()), _ptr(wp), cout, cin, 1 if transpose_flip else 0, _stream())
+    return _wcache.get((id(weight), bool(transpose_flip)), (weight,), build, "isrConvPrepareWeights")
 
 
 # Optional per-dispatch timing for bench.py: the library attaches start/stop events to the
@@ -440,18 +441,14 @@ _small_cache = _WeightImages(64)
 def _prepare_small(weight, bias):
     """(w8, bias8) device tensors for the Cout <= 8 kernel, cached like prepare_weights."""
     lib = _sr()
-    hit = _small_cache.lookup(id(weight), (weight, bias))
-    if hit is not None:
-        return hit
-    cout, cin = weight.shape[0], weight.shape[1]
-    w8 = torch.empty(lib.isrConvSmallWeightFloats(cin), dtype=torch.float32, device=weight.device)
-    b8 = torch.empty(8, dtype=torch.float32, device=weight.device)
-    rc = lib.isrConvSmallPrepare(_ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()) if bias is not None else None,
-                                 _ptr(w8), _ptr(b8), cout, cin, _stream())
-    if rc != 0:
-        raise RuntimeError("isrConvSmallPrepare failed (%d)" % rc)
-    _small_cache.store(id(weight), (weight, bias), (w8, b8))
-    return w8, b8
+
+    def build():
+        cout, cin = weight.shape[0], weight.shape[1]
+        w8 = torch.empty(lib.isrConvSmallWeightFloats(cin), dtype=torch.float32, device=weight.device)
+        b8 = torch.empty(8, dtype=torch.float32, device=weight.device)
+        return (w8, b8), lib.isrConvSmallPrepare(_ptr(weight.detach().contiguous()), _ptr(bias.detach().contiguous()) if bias is not None else None,
+                                                 _ptr(w8), _ptr(b8), cout, cin, _stream())
+    return _small_cache.get(id(weight), (weight, bias), build, "isrConvSmallPrepare")
 
 
 def _launch_small(x, weight, bias, residual, act, slope):
@@ -531,21 +528,16 @@ def _prepare_lp(weight, transpose_flip=False, bf16=False):
     """Weights in the low-precision kernel's layout (fp16, or bf16 for the training mode); transpose_flip: the
     data-gradient weights w'[ci][co][ky][kx] = w[co][ci][2-ky][2-kx]."""
     lib = _sr()
-    key = (id(weight), bool(transpose_flip), bool(bf16))
-    wq = _f16_cache.lookup(key, (weight,))
-    if wq is not None:
-        return wq
-    w = weight.detach()
-    if transpose_flip:
-        w = w.flip(2, 3).transpose(0, 1)
-    w = w.contiguous()
-    cout, cin = w.shape[0], w.shape[1]
-    wq = torch.empty(lib.isrConvF16WeightBytes(cin, cout), dtype=torch.uint8, device=weight.device)
-    rc = (lib.isrConvBf16Prepare if bf16 else lib.isrConvF16Prepare)(_ptr(w), _ptr(wq), cout, cin, _stream())
-    if rc != 0:
-        raise RuntimeError("isrConv%sPrepare failed (%d)" % ("Bf16" if bf16 else "F16", rc))
-    _f16_cache.store(key, (weight,), wq)
-    return wq
+
+    def build():
+        w = weight.detach()
+        if transpose_flip:
+            w = w.flip(2, 3).transpose(0, 1)
+        w = w.contiguous()
+        cout, cin = w.shape[0], w.shape[1]
+        wq = torch.empty(lib.isrConvF16WeightBytes(cin, cout), dtype=torch.uint8, device=weight.device)
+        return wq, (lib.isrConvBf16Prepare if bf16 else lib.isrConvF16Prepare)(_ptr(w), _ptr(wq), cout, cin, _stream())
+    return _f16_cache.get((id(weight), bool(transpose_flip), bool(bf16)), (weight,), build, "isrConv%sPrepare" % ("Bf16" if bf16 else "F16"))
 
 
 def _launch_lp(symbol, x, wq, bias, residual, cout, act, slope, upsample2x, packed=False):
@@ -786,21 +778,17 @@ def _prepare_split(weight, transpose_flip=False):
     """Weights as scaled (hi, lo) fp16 pairs in the split kernel's layout, cached like ``prepare_weights``;
     transpose_flip: the data-gradient weights w'[ci][co][ky][kx] = w[co][ci][2-ky][2-kx]."""
     lib = _sr()
-    key = (id(weight), bool(transpose_flip))
-    wq = _split_cache.lookup(key, (weight,))
-    if wq is not None:
-        return wq
-    w = weight.detach()
-    if transpose_flip:
-        w = w.flip(2, 3).transpose(0, 1)
-    w = w.contiguous()
-    cout, cin = w.shape[0], w.shape[1]
-    wq = torch.empty(lib.isrConvSplitWeightBytes(cin, cout), dtype=torch.uint8, device=weight.device)
-    rc = lib.isrConvSplitPrepare(_ptr(w), _ptr(wq), cout, cin, _stream())
-    if rc != 0:
-        raise RuntimeError("isrConvSplitPrepare failed (%d)" % rc)
-    _split_cache.store(key, (weight,), wq)
-    return wq
+
+    def build():
+        w = weight.detach().contiguous()
+        cout, cin = w.shape[0], w.shape[1]
+        if not transpose_flip:
+            wq = torch.empty(lib.isrConvSplitWeightBytes(cin, cout), dtype=torch.uint8, device=weight.device)
+            return wq, lib.isrConvSplitPrepare(_ptr(w), _ptr(wq), cout, cin, _stream())
+        wq = torch.empty(lib.isrConvSplitWeightBytes(cout, cin), dtype=torch.uint8, device=weight.device)
+        return wq, lib.isrConvSplitPrepareMany(1, (ctypes.c_void_p * 1)(w.data_ptr()), None, (ctypes.c_void_p * 1)(wq.data_ptr()),
+                                               (ctypes.c_int * 1)(cout), (ctypes.c_int * 1)(cin), _stream())
+    return _split_cache.get((id(weight), bool(transpose_flip)), (weight,), build, "isrConvSplitPrepareMany" if transpose_flip else "isrConvSplitPrepare")
 
 
 def _split_cached(weight, transpose_flip):
@@ -810,7 +798,7 @@ def _split_cached(weight, transpose_flip):
 def prepare_split_many(weights):
     """Bring the cached split-kernel images (forward AND data gradient) of all given [Cout, Cin, 3, 3] weights up to date in
     two launches (``isrConvSplitPrepareMany``).  A training step changes every weight, and preparing them one by one costs two
-    launches per image plus a flip and a copy for each data-gradient twin -- ~140 small launches per step for EnhanceNet."""
+    launches per image -- ~100 small launches per step for EnhanceNet."""
     lib = _sr()
     stale = [w for w in weights if w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
              and w.is_contiguous() and not (_split_cached(w, False) and _split_cached(w, True))]
@@ -1462,18 +1450,12 @@ def _prepare_convt(weight, layout="split"):
     """The [ci, co, 3, 3] weight of a ConvTranspose2d(64, 64, 3, 2, 1, 1) as the split kernel's image, cached like ``_prepare_split``.
     ``layout``: "split" the forward kernel's image, "dgrad" the data-gradient kernel's (ci and co trade places)."""
     lib = _sr()
-    key = (id(weight), layout)
-    wq = _convt_cache.lookup(key, (weight,))
-    if wq is not None:
-        return wq
-    size, prepare = (lib.isrConvTransposeDataGradWeightBytes, lib.isrConvTransposeDataGradPrepare) if layout == "dgrad" else \
-        (lib.isrConvTransposeSplitWeightBytes, lib.isrConvTransposeSplitPrepare)
-    wq = torch.empty(size(), dtype=torch.uint8, device=weight.device)
-    rc = prepare(_ptr(weight.detach().contiguous()), _ptr(wq), _stream())
-    if rc != 0:
-        raise RuntimeError("%s failed (%d)" % ("isrConvTransposeDataGradPrepare" if layout == "dgrad" else "isrConvTransposeSplitPrepare", rc))
-    _convt_cache.store(key, (weight,), wq)
-    return wq
+    name = "isrConvTransposeDataGrad" if layout == "dgrad" else "isrConvTransposeSplit"
+
+    def build():
+        wq = torch.empty(getattr(lib, name + "WeightBytes")(), dtype=torch.uint8, device=weight.device)
+        return wq, getattr(lib, name + "Prepare")(_ptr(weight.detach().contiguous()), _ptr(wq), _stream())
+    return _convt_cache.get((id(weight), layout), (weight,), build, name + "Prepare")
 
 
 _CONVT_TAPS = {0: ((1, 1),), 1: ((1, 2), (2, 0))}                 # phase bit -> ((r, k), ...): embedded row / column r holds tap k
@@ -2131,16 +2113,12 @@ def _prepare_tail(weight8):
     """The last layer's weights [6, 64, 3, 3] (colour networks: [3, 64, 3, 3]) by (tap, channel) row in the z stage's operand order,
     cached like ``prepare_weights``."""
     lib = _sr()
-    wz = _tail_cache.lookup(id(weight8), (weight8,))
-    if wz is not None:
-        return wz
-    wz = torch.empty(lib.isrConvTailWeightBytes(), dtype=torch.uint8, device=weight8.device)
-    prepare = lib.isrConvTailPrepare3 if weight8.shape[0] == 3 else lib.isrConvTailPrepare
-    rc = prepare(_ptr(weight8.detach().contiguous()), _ptr(wz), _stream())
-    if rc != 0:
-        raise RuntimeError("isrConvTailPrepare failed (%d)" % rc)
-    _tail_cache.store(id(weight8), (weight8,), wz)
-    return wz
+
+    def build():
+        wz = torch.empty(lib.isrConvTailWeightBytes(), dtype=torch.uint8, device=weight8.device)
+        prepare = lib.isrConvTailPrepare3 if weight8.shape[0] == 3 else lib.isrConvTailPrepare
+        return wz, prepare(_ptr(weight8.detach().contiguous()), _ptr(wz), _stream())
+    return _tail_cache.get(id(weight8), (weight8,), build, "isrConvTailPrepare")
 
 
 def tail_supported(features, weight6, weight8):
@@ -2248,17 +2226,12 @@ _upsp_cache = _WeightImages(64)
 def _prepare_ups_phase(weight):
     """The stacked image of the four effective weight sets of a [64, 64, 3, 3] weight (``isrConvUpsPhasePrepare``), cached per weight version."""
     lib = _sr()
-    wq = _upsp_cache.lookup(id(weight), (weight,))
-    if wq is not None:
-        return wq
-    w = weight.detach().contiguous()
-    wq = torch.empty(lib.isrConvUpsPhaseWeightBytes(), dtype=torch.uint8, device=weight.device)
-    scratch = torch.empty(lib.isrConvUpsPhaseScratchBytes(), dtype=torch.uint8, device=weight.device)
-    rc = lib.isrConvUpsPhasePrepare(_ptr(w), _ptr(wq), _ptr(scratch), _stream())
-    if rc != 0:
-        raise RuntimeError("isrConvUpsPhasePrepare failed (%d)" % rc)
-    _upsp_cache.store(id(weight), (weight,), wq)
-    return wq
+
+    def build():
+        wq = torch.empty(lib.isrConvUpsPhaseWeightBytes(), dtype=torch.uint8, device=weight.device)
+        scratch = torch.empty(lib.isrConvUpsPhaseScratchBytes(), dtype=torch.uint8, device=weight.device)
+        return wq, lib.isrConvUpsPhasePrepare(_ptr(weight.detach().contiguous()), _ptr(wq), _ptr(scratch), _stream())
+    return _upsp_cache.get(id(weight), (weight,), build, "isrConvUpsPhasePrepare")
 
 
 def pack_split(x):

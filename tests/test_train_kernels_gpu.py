@@ -774,19 +774,41 @@ def test_residual_reconstruction_kernel_matches_interpolate_add_cat(shape):
 
 def test_batched_weight_preparation_equals_the_per_layer_one():
     """isrConvSplitPrepareMany (all layers, forward + data-gradient images, two launches) must write the very bytes that
-    isrConvSplitPrepare writes layer by layer (the data-gradient image there from a flipped / transposed copy)."""
+    isrConvSplitPrepare writes layer by layer -- and both the bytes of the host definition (split_image_common: one kernel serves both
+    entry points, so the independent side is the definition).  (6, 64), (3, 64): Cout padded to 32; (64, 6): one k-step, mostly
+    padding; 33 more weights: the 32-layer chunks of the batched call."""
     from isosurfacesuperresolution_amd import ops
+    from split_image_common import CONV_DGRAD, CONV_FORWARD, split_image
     g = torch.Generator().manual_seed(9)
-    shapes = [(64, 64), (64, 101), (32, 40), (64, 64), (16, 9)]
-    ws = [((torch.rand(co, ci, 3, 3, generator=g) - 0.5) * (10.0 ** (k - 2))).cuda() for k, (co, ci) in enumerate(shapes)]
+    shapes = [(64, 64), (64, 101), (32, 40), (64, 64), (16, 9), (6, 64), (3, 64), (64, 6)] + [(8, 8)] * 33
+    ws = [((torch.rand(co, ci, 3, 3, generator=g) - 0.5) * (10.0 ** (k % 8 - 2))).cuda() for k, (co, ci) in enumerate(shapes)]
     ref = [(ops._prepare_split(w, False).clone(), ops._prepare_split(w, True).clone()) for w in ws]
     ops._split_cache.clear()
     ops.prepare_split_many(ws)
     for w, (f, b) in zip(ws, ref):
         assert ops._split_cached(w, False) and ops._split_cached(w, True)
         assert torch.equal(ops._prepare_split(w, False), f) and torch.equal(ops._prepare_split(w, True), b)
+        assert torch.equal(f.cpu(), split_image(w, *CONV_FORWARD)) and torch.equal(b.cpu(), split_image(w, *CONV_DGRAD))
     # a weight that changes in place is stale again
     ws[1].add_(0.25)
     assert not ops._split_cached(ws[1], False)
     ops.prepare_split_many(ws)
     assert ops._split_cached(ws[1], False) and not torch.equal(ops._prepare_split(ws[1], False), ref[1][0])
+
+
+def test_weight_image_scale_at_the_edge_magnitudes():
+    """The header { 2^S, 2^-S, S, 0 } where the rule S = 13 - ilogb(max) does not apply as it stands: a zero maximum (S = 0, and an
+    all-zero image behind it), a tiny one (clamped to 100), an infinite one (S = 0)."""
+    from isosurfacesuperresolution_amd import ops
+    from split_image_common import header
+    zero = torch.zeros(8, 8, 3, 3).cuda()
+    tiny = torch.zeros(8, 8, 3, 3)
+    tiny[3, 5, 1, 2] = -1e-35
+    hot = torch.ones(8, 8, 3, 3)
+    hot[0, 1, 2, 0] = float("inf")
+    for w, S in ((zero, 0), (tiny.cuda(), 100), (hot.cuda(), 0)):
+        for flip in (False, True):
+            image = ops._prepare_split(w, flip).cpu()
+            assert bytes(image[:16].tolist()) == header(S)
+            if w is zero:
+                assert not image[16:].any()
