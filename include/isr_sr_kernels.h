@@ -144,12 +144,11 @@ void isrSetMaxSlots(void* words, int capacity);
 int isrTakeMaxSlotWords(void);
 /* ...SplitMax: as ...Split, with the maxima of the gz tensors supplied: gzmax[k] (HOST array of device pointers) -> maxWords words
  * whose maximum is the bit pattern of max |gzs[k]|, as left by the kernel that produced the tensor (isrResBlockSmall's zmax /
- * ymax, isrSetMaxSlots: one word per wave); the pass over gz that ...Split makes to find its scale is skipped.  gzmax == NULL: exactly ...Split. */
+ * ymax, isrSetMaxSlots: one word per wave); the pass over gz that ...Split makes to find its scale is skipped.
+ * accumulate: bit 0 -> dw += the gradient, bit 1 -> db += (instead of =), i.e. the slab reduction adds straight into a parameter's .grad;
+ * the same bits as the call followed by `grad += dw`.  gzmax == NULL and accumulate == 0: exactly ...Split. */
 int isrConv3x3WeightGradSegmentsSplitMax(const float* const* xs, const float* const* gzs, const void* const* gzmax, int maxWords, int segments,
-                                         float* dw, float* db, void* workspace, int N, int Cin, int H, int W, int Cout, void* stream);
-/* isrSetWeightGradAccumulate(bits) arms the NEXT ...SegmentsSplit / ...SplitMax call: bit 0 -> dw += the gradient, bit 1 -> db += (instead
- * of =), i.e. the slab reduction adds straight into a parameter's .grad; the same bits as the call followed by `grad += dw`. */
-void isrSetWeightGradAccumulate(int bits);
+                                         float* dw, float* db, int accumulate, void* workspace, int N, int Cin, int H, int W, int Cout, void* stream);
 int isrConv3x3WeightGradSegmentsBf16(const float* const* xs, const float* const* gzs, int segments, float* dw, float* db, void* workspace,
                                      int N, int Cin, int H, int W, int Cout, void* stream);
 

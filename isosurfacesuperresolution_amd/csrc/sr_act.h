@@ -1,4 +1,4 @@
-// The activation of an epilogue as a compile-time constant (round 6).  Included by sr_split_common.h and sr_conv3x3.hip.
+// The activation of an epilogue as a compile-time constant (round 6).  Included by sr_split_common.h (and through it by sr_conv3x3.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/isr_sr_kernels.h"

@@ -1,4 +1,4 @@
-// Per-dispatch timing shared by the translation units of libisr_sr.so (bench.py reads it through isrProfile*):
+// Per-dispatch timing shared by the translation units of libisr_sr.so (bench.py reads it through isrProfile*; implemented in sr_profile.hip):
 // while profiling is enabled, a launcher asks for a start/stop event pair that rides on its dispatch packet
 // and registers the launch's kernel variant and algorithmic flops.  Also the host-side helpers every launcher shares: the launch
 // itself, the CU count, the LDS opt-in.
@@ -24,7 +24,7 @@ constexpr int ISR_VARIANT_TAIL_FINISH = 27;    // tail_s_finish_kernel / tail_se
 constexpr int ISR_VARIANT_FLOW_FILL = 28;      // flow_fill_one_kernel / flow_fill_kernel (sr_frame.hip; the frame pipeline runs it on the render stream)
 constexpr int ISR_VARIANT_FINISH = 29;         // finish_frame_kernel (sr_frame.hip)
 constexpr int ISR_VARIANT_UPS_FRAME = 30;      // ups_frame_kernel (sr_conv_upsp.h): the one-pixel frame of a phase-decomposed upsampling layer
-constexpr int ISR_VARIANT_WGRAD_SPLIT = 32;    // conv3x3_wgrad_split2_kernel / conv3x3_wgrad_split_kernel (sr_conv3x3.hip): the split-operand weight gradient of one 64 x 64 channel block
+constexpr int ISR_VARIANT_WGRAD_SPLIT = 32;    // conv3x3_wgrad_split2_kernel / conv3x3_wgrad_split_kernel (sr_wgrad.hip): the split-operand weight gradient of one 64 x 64 channel block
 constexpr int ISR_VARIANT_SPLIT_UPSP = 31;     // conv3x3_split_upsp_kernel (sr_conv_upsp.h); NOT a "small" kernel: recorded at level 1
 // the colour networks' frame kernels (inference/loadedmodel.py, the colour branch)
 constexpr int ISR_VARIANT_SPLIT_TAIL_COLOUR = 33;  // conv3x3_split_tail_kernel<2, ., 3> (sr_conv_tail.hip): recorded at level 1, like the six-channel tail

@@ -2,7 +2,7 @@
 // gradient) is multiplied by 2^S before it is split into (hi, lo) fp16 pairs, with max |v| 2^S in [2^13, 2^14): hi stays far below the
 // fp16 overflow and lo stays a normal number; the consumer undoes it exactly with 2^-S.  Every prepared weight image starts with the
 // 16-byte header { 2^S, 2^-S, S, 0 }; the weight-gradient kernels keep the pair { 2^S, 2^-S } alone.
-// Needs nothing of the split kernels' parameter blocks: sr_conv3x3.hip includes it too.
+// Needs nothing of the split kernels' parameter blocks: sr_wgrad.hip includes it too.
 #pragma once
 #include <hip/hip_runtime.h>
 

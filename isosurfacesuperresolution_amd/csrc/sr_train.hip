@@ -722,6 +722,32 @@ __global__ __launch_bounds__(256) void recurrent_input_post_kernel(const RecurPa
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Gradient through an activation: gz = gy where y > 0 (or no activation), gy * slope elsewhere (slope 0 for ReLU)
+// ---------------------------------------------------------------------------------------------------------
+__global__ void act_backward_kernel(const float* __restrict__ gy, const float* __restrict__ y, float* __restrict__ gz,
+                                    long long count, int act, float slope)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x * 4;
+    for (long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; e < count; e += stride) {
+        if (e + 3 < count) {
+            const float4 g = *reinterpret_cast<const float4*>(gy + e);
+            const float4 o = *reinterpret_cast<const float4*>(y + e);
+            float4 r;
+            const float s = act == ISR_ACT_RELU ? 0.f : slope;
+            r.x = o.x > 0.f ? g.x : g.x * s; r.y = o.y > 0.f ? g.y : g.y * s;
+            r.z = o.z > 0.f ? g.z : g.z * s; r.w = o.w > 0.f ? g.w : g.w * s;
+            if (act == ISR_ACT_NONE) r = g;
+            *reinterpret_cast<float4*>(gz + e) = r;
+        } else {
+            for (long long k = e; k < count; ++k) {
+                const float s = act == ISR_ACT_RELU ? 0.f : slope;
+                gz[k] = (act == ISR_ACT_NONE || y[k] > 0.f) ? gy[k] : gy[k] * s;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Phase-major gradient of the stride-2 transposed convolution (csrc/sr_conv_transpose.hip)
 // ---------------------------------------------------------------------------------------------------------
 // G[n][4 c + 2 a + b][i][j] = gz[n][c][2i + a][2j + b], gz = gy where y > 0 (or no activation), gy * slope elsewhere (slope 0 for
@@ -785,6 +811,17 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, c
 __global__ void adam_flat_count_kernel(float* step) { step[0] += 1.0f; }
 
 extern "C" {
+
+int isrActBackward(const float* gy, const float* y, float* gz, long long count, int act, float slope, void* stream)
+{
+    if (!gy || !y || !gz || count < 0) return -1;
+    if (count == 0) return 0;
+    long long blocks = (count / 4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(act_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, gy, y, gz, count, act, slope);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 int isrAdamFlatStep(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, const float* lr_dev, float lr,
                     float beta1, float beta2, float eps, float* step, void* stream)

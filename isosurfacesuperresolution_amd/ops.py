@@ -73,10 +73,9 @@ def _bind(lib):
     lib.isrActBackward.argtypes = [vp, vp, vp, ll, ci, cf, vp]; lib.isrActBackward.restype = ci
     lib.isrResBlockSmallSupported.argtypes = [ci, ci, ci]; lib.isrResBlockSmallSupported.restype = ci
     lib.isrResBlockSmall.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]; lib.isrResBlockSmall.restype = ci
-    lib.isrConv3x3WeightGradSegmentsSplitMax.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    lib.isrConv3x3WeightGradSegmentsSplitMax.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp]
     lib.isrConv3x3WeightGradSegmentsSplitMax.restype = ci
     lib.isrSetMaxSlots.argtypes = [vp, ci]; lib.isrSetMaxSlots.restype = None
-    lib.isrSetWeightGradAccumulate.argtypes = [ci]; lib.isrSetWeightGradAccumulate.restype = None
     lib.isrTakeMaxSlotWords.argtypes = []; lib.isrTakeMaxSlotWords.restype = ci
     lib.isrAssembleInput.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]; lib.isrAssembleInput.restype = ci
     lib.isrAssembleInputRows.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]; lib.isrAssembleInputRows.restype = ci
@@ -918,35 +917,50 @@ def _wgrad_workspace(device, nbytes):
     return ws
 
 
-def _weight_grad(xs, gzs, weight, has_bias):
-    """(dw, db) summed over the pairs (xs[k], gzs[k]) -- ``isrConv3x3WeightGradSegments``, one pass per <= 32 pairs."""
+def _wgrad_kind(xs, gzs, weight):
+    """Which weight-gradient kernels take these pairs.  "bf16" (the mixed-precision mode) and "split" need enough 4x32-pixel tiles to
+    stream (the kernels are memory bound), W % 4 == 0 and 16-byte aligned gradients; everything else is "exact"."""
+    n, _, h, w = xs[0].shape
+    tiles = n * len(xs) * ((h + 3) // 4) * ((w + 31) // 32)
+    big = w % 4 == 0 and tiles >= 1024 and all(t.data_ptr() % 16 == 0 for t in gzs)
+    if TRAIN_BF16 and big and weight.shape[0] > 8:
+        return "bf16"
+    # (the split kernel also takes the 64 -> 6 output layer: its 32-row MFMA tile is mostly padding there, but at a
+    # fifth of the matrix cycles it still beats the fp32 K-split kernel)
+    return "split" if (TRAIN_SPLIT and big) else "exact"
+
+
+def _wgrad_segments(xs, gzs, weight, dw, db, accumulate=0):
+    """One weight-gradient pass over at most 32 pairs (xs[k], gzs[k]) into dw / db; returns the entry point's code.  The split kind
+    takes the maxima the producers of gzs left behind (``_gmax_of``) and ``accumulate`` (bit 0: dw +=, bit 1: db +=)."""
     lib = _sr()
     cout, cin = weight.shape[0], weight.shape[1]
     n, _, h, w = xs[0].shape
+    kind = _wgrad_kind(xs, gzs, weight)
+    if accumulate and kind != "split":
+        raise RuntimeError("only the split-operand weight gradient accumulates")
     ws = _wgrad_workspace(weight.device, lib.isrConvWeightGradWorkspace(n, cin, h, w, cout))
-    most = lib.isrConvWeightGradMaxSegments()
+    px = (ctypes.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
+    pg = (ctypes.c_void_p * len(gzs))(*[t.data_ptr() for t in gzs])
+    _tally(kind, 2.0 * 9 * cin * cout * n * len(xs) * h * w)
+    shape = (_ptr(ws), n, cin, h, w, cout, _stream())
+    if kind != "split":
+        fn = lib.isrConv3x3WeightGradSegmentsBf16 if kind == "bf16" else lib.isrConv3x3WeightGradSegments
+        return fn(px, pg, len(xs), _ptr(dw), _ptr(db), *shape)
+    maxima = [_gmax_of(t) for t in gzs]
+    tagged = all(m is not None for m in maxima) and len(set(m[1] for m in maxima)) == 1
+    pm = (ctypes.c_void_p * len(gzs))(*[m[0] for m in maxima]) if tagged else None
+    return lib.isrConv3x3WeightGradSegmentsSplitMax(px, pg, pm, maxima[0][1] if tagged else 0, len(xs), _ptr(dw), _ptr(db), accumulate, *shape)
+
+
+def _weight_grad(xs, gzs, weight, has_bias):
+    """(dw, db) summed over the pairs (xs[k], gzs[k]) -- ``isrConv3x3WeightGradSegments``, one pass per <= 32 pairs."""
+    most = _sr().isrConvWeightGradMaxSegments()
     gw = gb = None
     for k in range(0, len(xs), most):
-        part_x, part_g = xs[k:k + most], gzs[k:k + most]
         dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-        db = torch.empty(cout, dtype=torch.float32, device=weight.device) if has_bias else None
-        px = (ctypes.c_void_p * len(part_x))(*[t.data_ptr() for t in part_x])
-        pg = (ctypes.c_void_p * len(part_g))(*[t.data_ptr() for t in part_g])
-        # mixed-precision mode: bf16 operands once there are enough 4x32-pixel tiles to stream (the kernel is memory bound)
-        tiles = n * len(part_x) * ((h + 3) // 4) * ((w + 31) // 32)
-        big = w % 4 == 0 and tiles >= 1024 and all(t.data_ptr() % 16 == 0 for t in part_g)
-        # (the split kernel also takes the 64 -> 6 output layer: its 32-row MFMA tile is mostly padding there, but at a
-        # fifth of the matrix cycles it still beats the fp32 K-split kernel)
-        fn = lib.isrConv3x3WeightGradSegmentsBf16 if (TRAIN_BF16 and big and cout > 8) else (
-            lib.isrConv3x3WeightGradSegmentsSplit if (TRAIN_SPLIT and big) else lib.isrConv3x3WeightGradSegments)
-        _tally("bf16" if (TRAIN_BF16 and big and cout > 8) else ("split" if (TRAIN_SPLIT and big) else "exact"),
-               2.0 * 9 * cin * cout * n * len(part_x) * h * w)
-        maxima = [_gmax_of(t) for t in part_g] if fn is lib.isrConv3x3WeightGradSegmentsSplit else [None]
-        if all(m is not None for m in maxima) and len(set(m[1] for m in maxima)) == 1:
-            pm = (ctypes.c_void_p * len(part_g))(*[m[0] for m in maxima])
-            rc = lib.isrConv3x3WeightGradSegmentsSplitMax(px, pg, pm, maxima[0][1], len(part_x), _ptr(dw), _ptr(db), _ptr(ws), n, cin, h, w, cout, _stream())
-        else:
-            rc = fn(px, pg, len(part_x), _ptr(dw), _ptr(db), _ptr(ws), n, cin, h, w, cout, _stream())
+        db = torch.empty(weight.shape[0], dtype=torch.float32, device=weight.device) if has_bias else None
+        rc = _wgrad_segments(xs[k:k + most], gzs[k:k + most], weight, dw, db)
         if rc != 0:
             raise RuntimeError("isrConv3x3WeightGradSegments failed (%d)" % rc)
         gw = dw if gw is None else gw + dw
@@ -1035,7 +1049,7 @@ class deferred_weight_gradients:
 
 
 # The deferred pass writes straight into .grad: a layer that takes the split-operand kernel in one piece (<= 32 frames) has its slab
-# reduction ADD to the parameters' gradients (isrSetWeightGradAccumulate) instead of producing dw / db for a `grad += dw` launch per
+# reduction ADD to the parameters' gradients (the `accumulate` argument of isrConv3x3WeightGradSegmentsSplitMax) instead of producing dw / db for a `grad += dw` launch per
 # parameter (47 launches per step).  Same sums, same roundings (tests/test_train_kernels_gpu.py).  (Tried: the weight-gradient kernels
 # of all layers back to back and ONE reduction launch at the end -- 71 launches fewer, the same step time: the slabs, 38 MB per layer,
 # then come back from memory instead of the caches.)
@@ -1044,12 +1058,8 @@ WGRAD_INTO_GRAD = os.environ.get("ISR_WGRAD_INTO_GRAD", "1") != "0"
 
 def _weight_grad_into_grad(xs, gzs, weight, bias):
     """The layer's weight (and bias) gradient added to ``weight.grad`` / ``bias.grad`` by the reduction itself; False: not eligible."""
-    lib = _sr()
-    cout, cin = weight.shape[0], weight.shape[1]
-    n, _, h, w = xs[0].shape
-    tiles = n * len(xs) * ((h + 3) // 4) * ((w + 31) // 32)
-    if not (WGRAD_INTO_GRAD and TRAIN_SPLIT and not TRAIN_BF16 and len(xs) <= lib.isrConvWeightGradMaxSegments()
-            and w % 4 == 0 and tiles >= 1024 and all(t.data_ptr() % 16 == 0 for t in gzs)):
+    if not (WGRAD_INTO_GRAD and not TRAIN_BF16 and len(xs) <= _sr().isrConvWeightGradMaxSegments()
+            and _wgrad_kind(xs, gzs, weight) == "split"):
         return False
     bits = 0
     for k, param in enumerate((weight, bias)):
@@ -1061,18 +1071,7 @@ def _weight_grad_into_grad(xs, gzs, weight, bias):
             param.grad = torch.empty_like(param, memory_format=torch.contiguous_format)
         else:
             bits |= 1 << k
-    ws = _wgrad_workspace(weight.device, lib.isrConvWeightGradWorkspace(n, cin, h, w, cout))
-    px = (ctypes.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
-    pg = (ctypes.c_void_p * len(gzs))(*[t.data_ptr() for t in gzs])
-    maxima = [_gmax_of(t) for t in gzs]
-    if all(m is not None for m in maxima) and len(set(m[1] for m in maxima)) == 1:
-        pm, words = (ctypes.c_void_p * len(gzs))(*[m[0] for m in maxima]), maxima[0][1]
-    else:
-        pm, words = None, 0
-    _tally("split", 2.0 * 9 * cin * cout * n * len(xs) * h * w)
-    lib.isrSetWeightGradAccumulate(bits)
-    rc = lib.isrConv3x3WeightGradSegmentsSplitMax(px, pg, pm, words, len(xs), _ptr(weight.grad), _ptr(bias.grad if bias is not None else None),
-                                                  _ptr(ws), n, cin, h, w, cout, _stream())
+    rc = _wgrad_segments(xs, gzs, weight, weight.grad, bias.grad if bias is not None else None, bits)
     if rc != 0:
         raise RuntimeError("isrConv3x3WeightGradSegmentsSplitMax failed (%d)" % rc)
     return True

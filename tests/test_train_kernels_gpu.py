@@ -610,7 +610,7 @@ def test_weight_gradient_scale_from_the_producers_maxima_is_bit_identical():
 
 
 def test_slab_reduction_into_grad_is_bit_identical():
-    """ops.WGRAD_INTO_GRAD: the deferred layers' slab reductions add straight into .grad (isrSetWeightGradAccumulate), against
+    """ops.WGRAD_INTO_GRAD: the deferred layers' slab reductions add straight into .grad (the accumulate argument), against
     `grad += dw` per parameter -- with gradients already present (second clip accumulates onto the first) and absent."""
     from isosurfacesuperresolution_amd import ops
     g = torch.Generator().manual_seed(9)
@@ -644,6 +644,107 @@ def test_slab_reduction_into_grad_is_bit_identical():
     for k, (a, b) in enumerate(zip(out[True], out[False])):
         assert torch.equal(a, b), "parameter %d: %g" % (k, (a - b).abs().max().item())
         assert a.abs().max().item() > 0
+
+
+def _wgrad_abi(entry, xs, gzs, dw, db, shape, accumulate=0, segments=None):
+    """One call of a weight-gradient entry point of the C ABI (no ops routing: the many-tiles threshold lives in ops only); the return code.
+    xs / gzs may hold None (a NULL pair); ``segments`` overrides the count handed to the library."""
+    import ctypes
+    from isosurfacesuperresolution_amd import ops
+    lib = ops._sr()
+    n, cin, h, w, cout = shape
+    ws = ops._wgrad_workspace(dw.device, lib.isrConvWeightGradWorkspace(n, cin, h, w, cout))
+    px = (ctypes.c_void_p * len(xs))(*[None if t is None else t.data_ptr() for t in xs])
+    pg = (ctypes.c_void_p * len(gzs))(*[None if t is None else t.data_ptr() for t in gzs])
+    segs = len(xs) if segments is None else segments
+    tail = (ops._ptr(ws), n, cin, h, w, cout, ops._stream())
+    if entry == "splitmax":
+        rc = lib.isrConv3x3WeightGradSegmentsSplitMax(px, pg, None, 0, segs, ops._ptr(dw), ops._ptr(db), accumulate, *tail)
+    else:
+        fn = {"exact": lib.isrConv3x3WeightGradSegments, "bf16": lib.isrConv3x3WeightGradSegmentsBf16, "split": lib.isrConv3x3WeightGradSegmentsSplit}[entry]
+        rc = fn(px, pg, segs, ops._ptr(dw), ops._ptr(db), *tail)
+    torch.cuda.synchronize()
+    return rc
+
+
+def _wgrad_pairs(segs, n, cin, cout, h, w, seed):
+    g = torch.Generator().manual_seed(seed)
+    xs = [torch.relu(torch.randn(n, cin, h, w, generator=g)).cuda() for _ in range(segs)]
+    gzs = [(torch.randn(n, cout, h, w, generator=g) * 1e-2).cuda() for _ in range(segs)]
+    return xs, gzs, g
+
+
+@pytest.mark.parametrize("cin,cout", [(12, 64), (64, 6), (64, 64)])
+def test_weight_gradient_accumulate_bits(cin, cout):
+    """isrConv3x3WeightGradSegmentsSplitMax(..., accumulate): a set bit (0: dw, 1: db) adds the gradient to what the tensor held with
+    one fp32 add per element, a clear bit overwrites it; db == NULL with bit 1 set is a valid call.  5 x 36 pixels: a ragged last
+    tile in both directions."""
+    n, h, w = 1, 5, 36
+    shape = (n, cin, h, w, cout)
+    xs, gzs, g = _wgrad_pairs(2, n, cin, cout, h, w, 11 * cin + cout)
+    pre_w = ((torch.rand(cout, cin, 3, 3, generator=g) - 0.5) * 0.7).cuda()
+    pre_b = ((torch.rand(cout, generator=g) - 0.5) * 0.3).cuda()
+    plain_w, plain_b = pre_w.clone(), pre_b.clone()
+    assert _wgrad_abi("splitmax", xs, gzs, plain_w, plain_b, shape, 0) == 0
+    assert plain_w.abs().max().item() > 0 and plain_b.abs().max().item() > 0
+    assert not torch.equal(plain_w, pre_w) and not torch.equal(plain_b, pre_b)
+    for bits in (0, 1, 2, 3):
+        want_w = pre_w + plain_w if bits & 1 else plain_w
+        want_b = pre_b + plain_b if bits & 2 else plain_b
+        dw, db = pre_w.clone(), pre_b.clone()
+        assert _wgrad_abi("splitmax", xs, gzs, dw, db, shape, bits) == 0
+        assert torch.equal(dw, want_w), (bits, (dw - want_w).abs().max().item())
+        assert torch.equal(db, want_b), (bits, (db - want_b).abs().max().item())
+        if bits & 2:
+            dw = pre_w.clone()
+            assert _wgrad_abi("splitmax", xs, gzs, dw, None, shape, bits) == 0
+            assert torch.equal(dw, want_w), (bits, (dw - want_w).abs().max().item())
+
+
+def test_refused_weight_gradient_call_arms_nothing():
+    """A call the validation refuses (W = 6: -3) with accumulate = 3 leaves nothing behind: the next valid call with accumulate = 0 into
+    sentinel-filled tensors gives what the same call gives alone."""
+    n, cin, cout, h, w = 1, 12, 64, 5, 36
+    shape = (n, cin, h, w, cout)
+    xs, gzs, _ = _wgrad_pairs(2, n, cin, cout, h, w, 3)
+    alone_w, alone_b = torch.full((cout, cin, 3, 3), 7.0).cuda(), torch.full((cout,), 7.0).cuda()
+    assert _wgrad_abi("splitmax", xs, gzs, alone_w, alone_b, shape, 0) == 0
+    xs6, gzs6, _ = _wgrad_pairs(2, n, cin, cout, h, 6, 4)
+    dw, db = torch.full((cout, cin, 3, 3), 5.0).cuda(), torch.full((cout,), 5.0).cuda()
+    assert _wgrad_abi("splitmax", xs6, gzs6, dw, db, (n, cin, h, 6, cout), 3) == -3
+    assert dw.eq(5.0).all().item() and db.eq(5.0).all().item()
+    dw.fill_(7.0); db.fill_(7.0)
+    assert _wgrad_abi("splitmax", xs, gzs, dw, db, shape, 0) == 0
+    assert torch.equal(dw, alone_w) and torch.equal(db, alone_b)
+    assert alone_w.abs().max().item() > 0
+
+
+@pytest.mark.parametrize("entry", ["exact", "bf16", "split"])
+def test_weight_gradient_entry_points_share_one_validation(entry):
+    """Return codes of the three kinds' entry points: -1 for a segment count outside 1 .. 32 and for a NULL pair; a gzs[k] that is not
+    16-byte aligned is -1 and W % 4 != 0 is -3 on the bf16 and split kinds, and both are fine for the exact kind."""
+    n, cin, cout, h, w = 1, 12, 6, 5, 36
+    shape = (n, cin, h, w, cout)
+    xs, gzs, g = _wgrad_pairs(2, n, cin, cout, h, w, 21)
+    dw, db = torch.zeros(cout, cin, 3, 3).cuda(), torch.zeros(cout).cuda()
+    quads = entry != "exact"
+    assert _wgrad_abi(entry, xs, gzs, dw, db, shape) == 0
+    want = dw.clone()
+    assert _wgrad_abi(entry, xs, gzs, dw, db, shape, segments=0) == -1
+    assert _wgrad_abi(entry, xs * 17, gzs * 17, dw, db, shape, segments=33) == -1
+    assert _wgrad_abi(entry, [xs[0], None], gzs, dw, db, shape) == -1
+    assert _wgrad_abi(entry, xs, [gzs[0], None], dw, db, shape) == -1
+    # gzs[0] four bytes past a 16-byte boundary: the same values one float further into a larger buffer
+    room = torch.zeros(gzs[0].numel() + 4, device="cuda")
+    shifted = room[1:1 + gzs[0].numel()].view_as(gzs[0])
+    shifted.copy_(gzs[0])
+    assert shifted.data_ptr() % 16 == 4
+    dw.zero_()
+    assert _wgrad_abi(entry, xs, [shifted, gzs[1]], dw, db, shape) == (-1 if quads else 0)
+    if not quads:
+        assert torch.equal(dw, want)
+    xs6, gzs6, _ = _wgrad_pairs(2, n, cin, cout, h, 6, 22)
+    assert _wgrad_abi(entry, xs6, gzs6, dw, db, (n, cin, h, 6, cout)) == (-3 if quads else 0)
 
 
 def test_relu_backward_folded_into_the_consumers_data_gradient():
