@@ -240,11 +240,25 @@ def test_conv3x3_is_exact_fma_chain_on_integers(conv_mode):
     assert torch.equal(y.cpu().double(), ref)
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 64, 32, 32, 'relu'), (1, 101, 64, 17, 23, 'relu'),
-                                   (2, 64, 6, 40, 24, 'none'), (1, 64, 64, 64, 96, 'none')])
+# shape -> the family of the training graph's forward and data-gradient launches and the kernel of the data gradient
+# (tests/train_route_common.py): the first four are too small for the split kernels (fewer than 128 two-row tiles, or W % 4 != 0)
+BACKWARD_ROUTES = {(2, 64, 64, 32, 32, 'relu'): ("exact", "conv3x3_rowsplit_kernel"), (1, 101, 64, 17, 23, 'relu'): ("exact", "conv3x3_rowsplit_kernel"),
+                   (2, 64, 6, 40, 24, 'none'): ("exact", "conv3x3_rowsplit_kernel"), (1, 64, 64, 64, 96, 'none'): ("exact", "conv3x3_rowsplit_kernel"),
+                   (4, 64, 64, 31, 36, 'relu'): ("split", "conv3x3_split_rows2_kernel"),          # 128 two-row tiles
+                   (3, 101, 64, 90, 228, 'relu'): ("split", "conv3x3_split_kernel<false>")}       # 288 tiles; data gradient 64 -> 101: two channel groups
+
+
+@pytest.mark.parametrize("shape", list(BACKWARD_ROUTES))
 def test_conv3x3_backward(shape):
+    """Values and gradients against fp64 autograd -- on the route the table above names: the forward and the data gradient of the
+    last two shapes run on the split-operand kernels, all others on the exact ones.  With a ReLU inside the operation the comparison
+    of the input gradient presumes that device and reference open the same ReLUs; that is asserted first, so a failure says which
+    of the two it is (seed 11: the smallest fp64 |pre-activation| of the 3.9 M of the largest shape is 2.8e-7, of the other ReLU
+    shapes 2.6e-7 and more, against an fp32 summation error near zero of a few 1e-8)."""
     from isosurfacesuperresolution_amd import ops
+    from train_route_common import EXACT_FORMS, SPLIT_FORMS, observed
     N, Cin, Cout, h, w, act = shape
+    family, dgrad_kernel = BACKWARD_ROUTES[shape]
     g = torch.Generator().manual_seed(11)
     x = (torch.rand(N, Cin, h, w, generator=g) * 2 - 1)
     wt = ((torch.rand(Cout, Cin, 3, 3, generator=g) * 2 - 1) / (3.0 * Cin ** 0.5))
@@ -256,9 +270,22 @@ def test_conv3x3_backward(shape):
         yr = F.relu(yr)
     yr.backward(gy.double())
     xg, wg, bg = (t.cuda().requires_grad_() for t in (x, wt, b))
-    y = ops.conv3x3(xg, wg, bg, act=act)
-    y.backward(gy.cuda())
+    y, forward_families, forward_names = observed(lambda: ops.conv3x3(xg, wg, bg, act=act))
+    _, backward_families, backward_names = observed(lambda: y.backward(gy.cuda()))
     torch.cuda.synchronize()
+    # the forward launch and the data gradient took the family the table names (the weight gradients of all six shapes are too small
+    # for theirs: "exact", and not recorded by name), the data gradient the kernel form
+    conv_forms = [k for k in backward_names if k in SPLIT_FORMS + EXACT_FORMS]
+    assert conv_forms == [dgrad_kernel], backward_names
+    if family == "split":
+        assert set(forward_families) == {"split"} and set(backward_families) == {"split", "exact"}, (forward_families, backward_families)
+        assert len(forward_names) == 1 and forward_names[0] in SPLIT_FORMS, forward_names
+        assert backward_families["split"] == forward_families["split"]          # the data gradient: as many flops as the forward launch
+    else:
+        assert set(forward_families) == {"exact"} and set(backward_families) == {"exact"}, (forward_families, backward_families)
+        assert len(forward_names) == 1 and forward_names[0] in EXACT_FORMS, forward_names
+    if act == 'relu':
+        assert torch.equal(y.detach().cpu() > 0, yr.detach() > 0), "a ReLU opened on one side only: the gradients are not comparable"
     assert (y.detach().cpu().double() - yr.detach()).abs().max() <= 1e-4
     assert (xg.grad.cpu().double() - xr.grad).abs().max() <= 1e-4
     scale = max(1.0, wr.grad.abs().max().item())

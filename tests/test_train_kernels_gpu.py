@@ -200,21 +200,41 @@ def test_deferred_weight_gradients_equal_per_frame_accumulation():
                 pass
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 12, 20), (1, 64, 9, 7), (3, 64, 32, 32)])
+@pytest.mark.parametrize("shape", [(2, 64, 12, 20), (1, 64, 9, 7), (3, 64, 32, 32), (8, 64, 32, 8)])
 def test_residual_block_function_matches_fp64(shape):
-    """ops.residual_block (one autograd node, gated data gradient + fused skip gradient) vs fp64 PyTorch."""
+    """ops.residual_block (one autograd node, gated data gradient + fused skip gradient) vs fp64 PyTorch.  The first three shapes
+    are too small for the split kernels: four launches of the exact ones.  (8, 64, 32, 8) -- 128 two-row tiles, W <= 32 -- takes
+    the fused small-image block (isrResBlockSmall) in both directions: conv3x3_split_block2_kernel twice.  Its seed is one for
+    which every fp64 pre-activation of the block's ReLU is further than 1e-5 from zero (about four seeds in ten are, found on the
+    CPU), asserted below: device and reference then open the same ReLUs and the 1e-4 bars need no allowance for one that switched."""
     from isosurfacesuperresolution_amd import ops
-    g = torch.Generator().manual_seed(21)
+    from train_route_common import BLOCK2, EXACT_FORMS, SPLIT_FORMS, observed
+    fused = shape == (8, 64, 32, 8)
+    g = torch.Generator().manual_seed(17 if fused else 21)
     n, c, h, w = shape
     x = torch.randn(shape, generator=g)
     ws = [torch.randn(c, c, 3, 3, generator=g) * 0.05 for _ in range(2)]
     bs = [torch.randn(c, generator=g) * 0.1 for _ in range(2)]
     gy = torch.randn(shape, generator=g)
     dev = [t.cuda().requires_grad_(True) for t in (x, ws[0], bs[0], ws[1], bs[1])]
-    y = ops.residual_block(*dev)
-    y.backward(gy.cuda())
+
+    def step():
+        out = ops.residual_block(*dev)
+        out.backward(gy.cuda())
+        return out
+
+    y, families, names = observed(step)
+    convs = [k for k in names if k in SPLIT_FORMS + EXACT_FORMS]
+    if fused:
+        assert convs == [BLOCK2, BLOCK2] and set(families) == {"split", "exact"}, (names, families)      # "exact": the weight gradients
+        assert families["split"] == 2 * 2 * 2.0 * 9 * 64 * 64 * n * h * w
+    else:
+        assert len(convs) == 4 and all(k in EXACT_FORMS for k in convs) and set(families) == {"exact"}, (names, families)
     ref = [t.double().requires_grad_(True) for t in (x, ws[0], bs[0], ws[1], bs[1])]
-    yr = ref[0] + F.conv2d(F.relu(F.conv2d(ref[0], ref[1], ref[2], padding=1)), ref[3], ref[4], padding=1)
+    z = F.conv2d(ref[0], ref[1], ref[2], padding=1)
+    if fused:
+        assert z.detach().abs().min().item() > 1e-5
+    yr = ref[0] + F.conv2d(F.relu(z), ref[3], ref[4], padding=1)
     yr.backward(gy.double())
     assert (y.detach().cpu().double() - yr.detach()).abs().max().item() <= 1e-4
     for a, b in zip(dev, ref):
@@ -804,6 +824,56 @@ def test_relu_backward_folded_into_the_consumers_data_gradient():
             assert c.n == expect, (fuse, c.n)
     finally:
         ops.GATE_FUSION = old
+
+
+@pytest.mark.parametrize("form,shape,kernel", [("rows2", (4, 31, 36), "conv3x3_split_rows2_kernel"), ("tile", (3, 90, 228), "conv3x3_split_kernel<false>"),
+                                               ("stream", (3, 90, 228), "conv3x3_split_stream_kernel"), ("rowsplit", (1, 9, 7), "conv3x3_rowsplit_kernel"),
+                                               ("tile4", (6, 30, 33), "conv3x3_fwd2_kernel<false,1>"), ("tile16", (10, 50, 130), "conv3x3_fwd2_kernel<false,4>")])
+def test_relu_backward_folded_into_the_data_gradient_on_every_kernel_form(form, shape, kernel, request):
+    """The bit-identity statement of the test above -- conv(relu) -> conv, every gradient with ops.GATE_FUSION equal to the unfused
+    graph's -- where the gated data gradient runs on each form of the split-operand and of the exact kernels (the 64 x 64 images
+    above take the 2-row form only): ragged last tile rows and columns, and the 'gate' epilogue of every kernel.  The first layer
+    has 101 inputs, so its data gradient is the two-channel-group launch.  The streaming form through the diagnostics build's
+    grid cap, as in test_train_routes_gpu.py."""
+    from isosurfacesuperresolution_amd import ops
+    from train_route_common import EXACT_FORMS, SPLIT_FORMS, observed
+    n, h, w = shape
+    g = torch.Generator().manual_seed(79)
+    x0 = (torch.rand(n, 101, h, w, generator=g) - 0.5).cuda()
+    ws = [((torch.rand(64, ci, 3, 3, generator=g) - 0.5) * 0.1).cuda() for ci in (101, 64)]
+    bs = [(torch.rand(64, generator=g) - 0.5).cuda() for _ in ws]
+    tgt = torch.rand(n, 64, h, w, generator=g).cuda()
+
+    def run(fuse):
+        ops.GATE_FUSION = fuse
+        x = x0.clone().requires_grad_(True)
+        wt = [t.clone().requires_grad_(True) for t in ws]
+        b = [t.clone().requires_grad_(True) for t in bs]
+        y2 = ops.conv3x3(ops.conv3x3(x, wt[0], b[0], act='relu'), wt[1], b[1])
+        loss = ((y2 - tgt) ** 2).mean()
+        _, families, names = observed(loss.backward)
+        # two data gradients on the form this case is about: the gated one of the second layer (64 -> 64), then the first layer's (64 -> 101)
+        assert [k for k in names if k in SPLIT_FORMS + EXACT_FORMS] == [kernel, kernel], (fuse, names)
+        assert ("split" if kernel in SPLIT_FORMS else "exact") in families, (fuse, families)
+        return [x.grad] + [t.grad for t in wt] + [t.grad for t in b]
+
+    lib = request.getfixturevalue("diag_lib") if form == "stream" else None
+    old = ops.GATE_FUSION
+    try:
+        if lib is not None:
+            lib.isrDebugSetSplitSmall(0)
+            lib.isrDebugSetSplitSlots(8)
+        ref = run(False)
+        got = run(True)
+    finally:
+        ops.GATE_FUSION = old
+        if lib is not None:
+            lib.isrDebugSetSplitSlots(0)
+            lib.isrDebugSetSplitSmall(1)
+    assert ops.debug_switches() == 0
+    for name, a, c in zip(("x", "w1", "w2", "b1", "b2"), ref, got):
+        assert torch.equal(a, c), (form, name, (a - c).abs().max().item())
+        assert a.abs().max().item() > 0
 
 
 def test_gate_fusion_steps_aside_when_the_intermediate_gradient_is_observed():
