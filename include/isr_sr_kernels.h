@@ -603,6 +603,40 @@ int isrShuffleTailColourSupported(int N, int C, int Cout, int h, int w, long lon
 int isrShuffleTailColour(const float* f, long long fPlane, long long fImage, const float* weight, const float* bias, float* out,
                          long long outPlane, long long outImage, int N, int C, int Cout, int h, int w, int clamp, void* stream);
 
+/* Their backward (same tensors, strides, limits and return codes; every sum in a fixed order, no floating-point atomics, no host
+ * synchronisation: the launches can be captured in a graph).
+ *
+ * Channel attention, given dy (dx IS dy: no entry point), the mean z and the gate s [N][64] of the forward (isrChannelPoolMean, `gate`):
+ *   isrChannelGateGradSums: workspace[n][c][s] (double, S as above) = the slab sums of dy * t, each product rounded to fp32 once; their sum
+ *     in index order, rounded to fp32, is ds[n][c].
+ *   isrChannelGateScaleBackward: every workgroup forms ds[64] of its image, du = ds * (s * (1 - s)), recomputes a and g from z as the forward
+ *     does, dg[j] = the fp64 sum over c of Wu[c][j] du[c] rounded to fp32, da = a > 0 ? dg : dg * slope, dz[c] = fmaf-chain over j of Wd[j][c] da[j]
+ *     from 0, and stores dt = dy * s + (float)(dz[c] / (H W)) as a separately rounded multiply and add.
+ *   isrChannelGateParamGrad: one workgroup; dWUp [64][4] = sum_n du g^T, dBUp [64] = sum_n du, dWDown [4][64] = sum_n da z^T,
+ *     dBDown [4] = sum_n da, each an fp64 sum over the images in index order, rounded to fp32 once.
+ * The tail, given dout [N][Cout][4h][4w]:
+ *   isrShuffleTailDataGrad: ONE launch; df[16 ci + 4 i + j][y][x] = dP[ci][4 y + i][4 x + j], dP an fp32 fmaf chain from 0 over (co, ky, kx)
+ *     in this nesting of w[co][ci][2 - ky][2 - kx] dout[co][Y + ky - 1][X + kx - 1] (zeros outside the image); the dout tile and its halo
+ *     are staged in LDS, the four-channel high-resolution gradient never exists in memory.
+ *   isrShuffleTailWeightGrad: TWO launches; per tile (tiles = isrShuffleTailGradTiles(N, h, w)) and output channel the 36 terms of
+ *     dw[co][ci][ky][kx] = sum dout[co][Y][X] P[ci][Y + ky - 1][X + kx - 1] and db[co] = sum dout[co] in fp64 -> workspace
+ *     double [tiles][Cout][37], then the tiles in index order and one rounding to fp32.  dBias may be NULL. */
+int isrChannelAttentionBackwardSupported(int N, int C, int R, int H, int W, long long plane, long long image);      /* each of dy, t, dt */
+int isrChannelGateGradSums(const float* dy, long long dyPlane, long long dyImage, const float* t, long long tPlane, long long tImage,
+                           int N, int C, int H, int W, int S, double* workspace, void* stream);
+int isrChannelGateScaleBackward(const float* dy, long long dyPlane, long long dyImage, float* dt, long long dtPlane, long long dtImage,
+                                const double* workspace, int S, const float* mean, const float* gate, const float* wDown, const float* bDown,
+                                const float* wUp, float slope, int N, int C, int R, int H, int W, void* stream);
+int isrChannelGateParamGrad(const double* workspace, int S, const float* mean, const float* gate, const float* wDown, const float* bDown,
+                            const float* wUp, float slope, float* dWDown, float* dBDown, float* dWUp, float* dBUp, int N, int C, int R,
+                            int H, int W, void* stream);
+int isrShuffleTailBackwardSupported(int N, int C, int Cout, int h, int w, long long fPlane, long long fImage, long long outPlane, long long outImage);
+int isrShuffleTailGradTiles(int N, int h, int w);
+int isrShuffleTailDataGrad(const float* dout, long long doutPlane, long long doutImage, const float* weight, float* df, long long dfPlane,
+                           long long dfImage, int N, int C, int Cout, int h, int w, void* stream);
+int isrShuffleTailWeightGrad(const float* dout, long long doutPlane, long long doutImage, const float* f, long long fPlane, long long fImage,
+                             int N, int C, int Cout, int h, int w, int tiles, double* workspace, float* dWeight, float* dBias, void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

@@ -18,7 +18,8 @@ residual reconstruction; the subtraction needs ``len(channel_mask) == output_cha
 (three outputs, mask [0, 1, 2]) only.
 
 On an MI355X every convolution is one ``ops.conv3x3`` launch (bias + LeakyReLU / residual in the epilogue), every block's attention
-two launches (``ops.channel_attention_residual``) and the tail one (``ops.pixel_shuffle4_conv``)."""
+two launches (``ops.channel_attention_residual``) and the tail one (``ops.pixel_shuffle4_conv``); under autograd the same launches
+run forward and each of the two has its own backward kernels (at most three launches per block, three for the tail)."""
 import re
 
 import torch
@@ -146,5 +147,9 @@ class RCAN(nn.Module):
     def forward(self, inputs):
         post = self.net['post']
         raw = ops.pixel_shuffle4_conv(self.forward_features(inputs), post.weight, post.bias)
-        residual = raw - F.interpolate(inputs[:, list(self.channel_mask), :, :], size=(raw.shape[2], raw.shape[3]), mode='bilinear')
+        mask = list(self.channel_mask)
+        # consecutive channels (the colour family's [0, 1, 2]) as a slice: the same values without the index tensor that a list builds on
+        # the host -- a copy to the device, which a HIP graph capture of the training step (train.GraphedTrainStep) does not allow
+        masked = inputs[:, mask[0]:mask[-1] + 1] if mask == list(range(mask[0], mask[0] + len(mask))) else inputs[:, mask, :, :]
+        residual = raw - F.interpolate(masked, size=(raw.shape[2], raw.shape[3]), mode='bilinear')
         return torch.clamp(raw, 0, 1), residual

@@ -20,6 +20,7 @@ import weakref
 import numpy as np
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _native
 
@@ -194,6 +195,17 @@ def _bind(lib):
         lib.isrChannelGateScaleAdd.restype = ci
         lib.isrShuffleTailColourSupported.argtypes = [ci, ci, ci, ci, ci, ll, ll, ll, ll]; lib.isrShuffleTailColourSupported.restype = ci
         lib.isrShuffleTailColour.argtypes = [vp, ll, ll, vp, vp, vp, ll, ll, ci, ci, ci, ci, ci, ci, vp]; lib.isrShuffleTailColour.restype = ci
+    if hasattr(lib, "isrChannelGateScaleBackward"):             # (likewise: their backward; without it they train on the torch composite)
+        lib.isrChannelAttentionBackwardSupported.argtypes = [ci, ci, ci, ci, ci, ll, ll]; lib.isrChannelAttentionBackwardSupported.restype = ci
+        lib.isrChannelGateGradSums.argtypes = [vp, ll, ll, vp, ll, ll, ci, ci, ci, ci, ci, vp, vp]; lib.isrChannelGateGradSums.restype = ci
+        lib.isrChannelGateScaleBackward.argtypes = [vp, ll, ll, vp, ll, ll, vp, ci, vp, vp, vp, vp, vp, cf, ci, ci, ci, ci, ci, vp]
+        lib.isrChannelGateScaleBackward.restype = ci
+        lib.isrChannelGateParamGrad.argtypes = [vp, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+        lib.isrChannelGateParamGrad.restype = ci
+        lib.isrShuffleTailBackwardSupported.argtypes = [ci, ci, ci, ci, ci, ll, ll, ll, ll]; lib.isrShuffleTailBackwardSupported.restype = ci
+        lib.isrShuffleTailGradTiles.argtypes = [ci, ci, ci]; lib.isrShuffleTailGradTiles.restype = ci
+        lib.isrShuffleTailDataGrad.argtypes = [vp, ll, ll, vp, vp, ll, ll, ci, ci, ci, ci, ci, vp]; lib.isrShuffleTailDataGrad.restype = ci
+        lib.isrShuffleTailWeightGrad.argtypes = [vp, ll, ll, vp, ll, ll, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]; lib.isrShuffleTailWeightGrad.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -392,7 +404,10 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  # the transposed convolution of the TecoGAN generator (csrc/sr_conv_transpose.hip)
                  37: "convt3x3s2_split_kernel", 38: "convt3x3s2_dgrad_split_kernel",
                  # RCAN's channel attention and pixel-shuffle tail (csrc/sr_attention.hip)
-                 39: "channel_pool_kernel", 40: "gate_scale_add_kernel", 41: "shuffle_tail_kernel"}
+                 39: "channel_pool_kernel", 40: "gate_scale_add_kernel", 41: "shuffle_tail_kernel",
+                 # ... and their backward
+                 42: "gate_grad_sum_kernel", 43: "gate_backward_kernel", 44: "gate_param_grad_kernel",
+                 45: "shuffle_tail_dgrad_kernel", 46: "shuffle_tail_wgrad_kernel", 47: "shuffle_tail_wgrad_sum_kernel"}
 
 
 def debug_switches():
@@ -2433,7 +2448,11 @@ def tail_conv_finish_colour(features, weight6, bias6, weight8, bias8, net_input,
 # ---- RCAN: channel attention and the pixel-shuffle tail (csrc/sr_attention.hip) -------------------------------------------------------------
 # The three pieces of models/rcan.py that are not convolutions.  Each function's CPU branch is its DEFINITION in plain torch (as
 # ``conv3x3``'s is); a device tensor without autograd takes the HIP kernels where ``*_supported`` says so and the same torch composite
-# (with a warning, once) where the kernels refuse; under autograd each IS the torch composite (there are no backward kernels for them).
+# (with a warning, once) where the kernels refuse.  Under autograd ``channel_attention_residual`` (without ``return_gate``) and
+# ``pixel_shuffle4_conv`` are ONE autograd node each on the same forward kernels -- the result has the bits of the no-grad call -- with their
+# own backward kernels (``_ChannelAttentionFunction``: at most three launches, ``_PixelShuffle4ConvFunction``: three) where
+# ``*_backward_supported`` says so, and the torch composite, silently, where it does not (CPU, fp64, other shapes, a library without the
+# backward entry points, ``return_gate``).  ``channel_pool`` on its own is the torch composite under autograd: nothing trains through it alone.
 ATTENTION_CHANNELS = 64
 ATTENTION_REDUCED = 4
 # False: the three ops run their torch composite on the device without a word (tools/bench_rcan.py's comparison: the same network with
@@ -2523,6 +2542,9 @@ def channel_attention_residual(x, t, w_down, b_down, w_up, b_up, slope=0.01, ret
     ``range_key``: the range guard's word this launch reports the largest |y| to (``_arm_range``; models/rcan.py hands in the word of
     the block's second convolution, so that a block costs one word): y is tagged with it, and a hot y sends its consumer to the exact
     kernels through ``conv3x3``'s routing; without a key y counts as of unknown range only if x or t do."""
+    if (x.is_cuda and ATTENTION_KERNELS and not return_gate and _any_requires_grad(x, t, w_down, b_down, w_up, b_up)
+            and channel_attention_backward_supported(x, t, w_down, b_down, w_up, b_up)):
+        return _ChannelAttentionFunction.apply(x, t, w_down, b_down, w_up, b_up, float(slope))
     if not x.is_cuda or _any_requires_grad(x, t, w_down, b_down, w_up, b_up) or not ATTENTION_KERNELS:
         return _channel_attention_cpu(x, t, w_down, b_down, w_up, b_up, slope, return_gate)
     if not channel_attention_supported(x, t, w_down, w_up):
@@ -2531,22 +2553,96 @@ def channel_attention_residual(x, t, w_down, b_down, w_up, b_up, slope=0.01, ret
         out = _channel_attention_cpu(x, t, w_down, b_down, w_up, b_up, slope, return_gate)
         (out[0] if return_gate else out)._isr_range_key = HOT          # nobody watched its range
         return out
-    lib = _sr()
     with torch.no_grad():
         unknown = HOT in (getattr(x, '_isr_range_key', None), getattr(t, '_isr_range_key', None))
-        t, tp, ti, slabs, ws = _pool_partials(t)
-        x, xp, xi = _plane_strides(x)
-        n, c, h, w = x.shape
-        y = empty_planes(n, c, h, w, x.device)
-        gate = torch.empty((n, c), dtype=torch.float32, device=x.device) if return_gate else None
-        wd, bd, wu, bu = (p.detach().contiguous() for p in (w_down, b_down, w_up, b_up))
-        key = _arm_range(range_key, x.device) if range_key is not None else None
-        rc = lib.isrChannelGateScaleAdd(_ptr(x), _ptr(t), _ptr(y), xp, xi, tp, ti, y.stride(1), c * y.stride(1), _ptr(ws), slabs,
-                                        _ptr(wd), _ptr(bd), _ptr(wu), _ptr(bu), float(slope), _ptr(gate), n, c, ATTENTION_REDUCED, h, w, _stream())
-        if rc != 0:
-            raise RuntimeError("isrChannelGateScaleAdd failed (%d)" % rc)
+        y, gate, key = _attention_forward(x, t, w_down, b_down, w_up, b_up, slope, return_gate, range_key)[:3]
         y._isr_range_key = HOT if unknown else key
         return (y, gate) if return_gate else y
+
+
+def _attention_forward(x, t, w_down, b_down, w_up, b_up, slope, want_gate, range_key, packed=False):
+    """The two forward launches -> (y, gate [N, 64] or None, the armed range word or None, t as the kernels read it, S, the pool's
+    workspace).  ``packed``: y is an ordinary contiguous tensor (the autograd node's output), else ``empty_planes``."""
+    lib = _sr()
+    t, tp, ti, slabs, ws = _pool_partials(t)
+    x, xp, xi = _plane_strides(x)
+    n, c, h, w = x.shape
+    y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device) if packed else empty_planes(n, c, h, w, x.device)
+    gate = torch.empty((n, c), dtype=torch.float32, device=x.device) if want_gate else None
+    wd, bd, wu, bu = (p.detach().contiguous() for p in (w_down, b_down, w_up, b_up))
+    key = _arm_range(range_key, x.device) if range_key is not None else None
+    rc = lib.isrChannelGateScaleAdd(_ptr(x), _ptr(t), _ptr(y), xp, xi, tp, ti, y.stride(1), c * y.stride(1), _ptr(ws), slabs,
+                                    _ptr(wd), _ptr(bd), _ptr(wu), _ptr(bu), float(slope), _ptr(gate), n, c, ATTENTION_REDUCED, h, w, _stream())
+    if rc != 0:
+        raise RuntimeError("isrChannelGateScaleAdd failed (%d)" % rc)
+    return y, gate, key, t, slabs, ws
+
+
+def channel_attention_backward_supported(x, t, w_down, b_down, w_up, b_up):
+    """``_ChannelAttentionFunction`` takes these operands: what the forward kernels take, fp32 biases on the device, and a library that
+    has the backward entry points."""
+    lib = _sr()
+    if not hasattr(lib, "isrChannelGateScaleBackward") or not channel_attention_supported(x, t, w_down, w_up):
+        return False
+    if not all(b.is_cuda and b.dtype == torch.float32 for b in (b_down, b_up)):
+        return False
+    n, c, h, w = t.shape
+    return all(lib.isrChannelAttentionBackwardSupported(n, c, ATTENTION_REDUCED, h, w, *s) for s in (_strides_of(t), (h * w, c * h * w)))
+
+
+class _ChannelAttentionFunction(torch.autograd.Function):
+    """y = x + t * s as ONE autograd node.  Forward: the two launches of the no-grad route (no range word armed: the training rule of
+    ``_train_conv``) and ``isrChannelPoolMean``; t, the mean z and the gate s are saved.  Backward: dx IS dy; ``isrChannelGateGradSums``
+    (ds = sum_hw dy t), ``isrChannelGateScaleBackward`` (dt, only if t needs a gradient) and ``isrChannelGateParamGrad`` (only if a
+    parameter of the perceptron does) -- nothing is launched when neither does."""
+
+    @staticmethod
+    def forward(ctx, x, t, w_down, b_down, w_up, b_up, slope):
+        y, gate, _, t, slabs, ws = _attention_forward(x, t, w_down, b_down, w_up, b_up, slope, True, None, packed=True)
+        n, c, h, w = t.shape
+        mean = torch.empty((n, c), dtype=torch.float32, device=t.device)
+        rc = _sr().isrChannelPoolMean(_ptr(ws), n, c, h, w, slabs, _ptr(mean), _stream())
+        if rc != 0:
+            raise RuntimeError("isrChannelPoolMean failed (%d)" % rc)
+        ctx.slope = slope
+        ctx.save_for_backward(t, mean, gate, w_down, b_down, w_up)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        t, mean, gate, w_down, b_down, w_up = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gx = gy if need[0] else None
+        if not any(need[1:6]):
+            return gx, None, None, None, None, None, None
+        lib = _sr()
+        n, c, h, w = t.shape
+        t, tp, ti = _plane_strides(t)
+        g, gp, gi = _plane_strides(gy)
+        if not lib.isrChannelAttentionBackwardSupported(n, c, ATTENTION_REDUCED, h, w, gp, gi):
+            g, gp, gi = gy.contiguous(), h * w, c * h * w
+        slabs = lib.isrChannelPoolSlabs(n, h, w)
+        ws = torch.empty(n * c * slabs, dtype=torch.float64, device=t.device)
+        rc = lib.isrChannelGateGradSums(_ptr(g), gp, gi, _ptr(t), tp, ti, n, c, h, w, slabs, _ptr(ws), _stream())
+        if rc != 0:
+            raise RuntimeError("isrChannelGateGradSums failed (%d)" % rc)
+        wd, bd, wu = (p.detach().contiguous() for p in (w_down, b_down, w_up))
+        dt = dwd = dbd = dwu = dbu = None
+        if need[1]:
+            dt = torch.empty((n, c, h, w), dtype=torch.float32, device=t.device)
+            rc = lib.isrChannelGateScaleBackward(_ptr(g), gp, gi, _ptr(dt), h * w, c * h * w, _ptr(ws), slabs, _ptr(mean), _ptr(gate),
+                                                 _ptr(wd), _ptr(bd), _ptr(wu), ctx.slope, n, c, ATTENTION_REDUCED, h, w, _stream())
+            if rc != 0:
+                raise RuntimeError("isrChannelGateScaleBackward failed (%d)" % rc)
+        if any(need[2:6]):
+            dwd, dbd, dwu, dbu = (torch.empty(s, dtype=torch.float32, device=t.device)
+                                  for s in ((ATTENTION_REDUCED, c), (ATTENTION_REDUCED,), (c, ATTENTION_REDUCED), (c,)))
+            rc = lib.isrChannelGateParamGrad(_ptr(ws), slabs, _ptr(mean), _ptr(gate), _ptr(wd), _ptr(bd), _ptr(wu), ctx.slope,
+                                             _ptr(dwd), _ptr(dbd), _ptr(dwu), _ptr(dbu), n, c, ATTENTION_REDUCED, h, w, _stream())
+            if rc != 0:
+                raise RuntimeError("isrChannelGateParamGrad failed (%d)" % rc)
+        return (gx, dt, dwd if need[2] else None, dbd if need[3] else None, dwu if need[4] else None, dbu if need[5] else None, None)
 
 
 def pixel_shuffle4_conv_supported(f, weight):
@@ -2568,7 +2664,12 @@ def _pixel_shuffle4_conv_cpu(f, weight, bias, clamp):
 def pixel_shuffle4_conv(f, weight, bias, clamp=False):
     """RCAN's tail: conv3x3(pixel_shuffle(f [N, 64, h, w], 4), weight [Cout, 4, 3, 3], padding 1) + bias -> [N, Cout, 4h, 4w], clamped
     to [0, 1] with ``clamp``.  HIP: one launch (``isrShuffleTailColour``), the shuffled four-channel tensor stays in LDS; per value an
-    fp32 fmaf chain over (ci, ky, kx) starting from the bias.  Under autograd: ``F.pixel_shuffle`` and ``F.conv2d``."""
+    fp32 fmaf chain over (ci, ky, kx) starting from the bias.  Under autograd: the same launch as one autograd node
+    (``_PixelShuffle4ConvFunction``; ``clamp`` is then ``torch.clamp`` behind it -- the same bits), or ``F.pixel_shuffle`` and
+    ``F.conv2d`` where ``pixel_shuffle4_conv_backward_supported`` says no."""
+    if f.is_cuda and ATTENTION_KERNELS and _any_requires_grad(f, weight, bias) and pixel_shuffle4_conv_backward_supported(f, weight, bias):
+        out = _PixelShuffle4ConvFunction.apply(f, weight, bias)
+        return torch.clamp(out, 0, 1) if clamp else out
     if not f.is_cuda or _any_requires_grad(f, weight, bias) or not ATTENTION_KERNELS:
         return _pixel_shuffle4_conv_cpu(f, weight, bias, clamp)
     if not pixel_shuffle4_conv_supported(f, weight):
@@ -2576,17 +2677,75 @@ def pixel_shuffle4_conv(f, weight, bias, clamp=False):
                    % (tuple(f.shape), tuple(weight.shape)))
         return _pixel_shuffle4_conv_cpu(f, weight, bias, clamp)
     with torch.no_grad():
-        f, fp, fi = _plane_strides(f)
+        return _tail_forward(f, weight, bias, clamp)[0]
+
+
+def _tail_forward(f, weight, bias, clamp):
+    """The forward launch -> (out, f as the kernel read it)."""
+    f, fp, fi = _plane_strides(f)
+    n, c, h, w = f.shape
+    cout = weight.shape[0]
+    out = torch.empty((n, cout, 4 * h, 4 * w), dtype=torch.float32, device=f.device)
+    wt = weight.detach().contiguous()
+    b = bias.detach().contiguous() if bias is not None else None
+    rc = _sr().isrShuffleTailColour(_ptr(f), fp, fi, _ptr(wt), _ptr(b), _ptr(out), 16 * h * w, cout * 16 * h * w, n, c, cout, h, w,
+                                    1 if clamp else 0, _stream())
+    if rc != 0:
+        raise RuntimeError("isrShuffleTailColour failed (%d)" % rc)
+    return out, f
+
+
+def pixel_shuffle4_conv_backward_supported(f, weight, bias):
+    """``_PixelShuffle4ConvFunction`` takes these operands: what the forward kernel takes, an fp32 bias on the device (or none), and a
+    library that has the backward entry points."""
+    lib = _sr()
+    if not hasattr(lib, "isrShuffleTailDataGrad") or not pixel_shuffle4_conv_supported(f, weight):
+        return False
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
+        return False
+    n, c, h, w = f.shape
+    cout = weight.shape[0]
+    return all(lib.isrShuffleTailBackwardSupported(n, c, cout, h, w, *s, 16 * h * w, cout * 16 * h * w) for s in (_strides_of(f), (h * w, c * h * w)))
+
+
+class _PixelShuffle4ConvFunction(torch.autograd.Function):
+    """out = conv3x3(pixel_shuffle(f, 4), w) + b as ONE autograd node: forward ``isrShuffleTailColour``; backward
+    ``isrShuffleTailDataGrad`` (one launch, only if f needs a gradient) and ``isrShuffleTailWeightGrad`` (two launches, only if the
+    weight or the bias does)."""
+
+    @staticmethod
+    def forward(ctx, f, weight, bias):
+        out, f = _tail_forward(f, weight, bias, False)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(f, weight)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        f, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        lib = _sr()
         n, c, h, w = f.shape
         cout = weight.shape[0]
-        out = torch.empty((n, cout, 4 * h, 4 * w), dtype=torch.float32, device=f.device)
-        wt = weight.detach().contiguous()
-        b = bias.detach().contiguous() if bias is not None else None
-        rc = _sr().isrShuffleTailColour(_ptr(f), fp, fi, _ptr(wt), _ptr(b), _ptr(out), 16 * h * w, cout * 16 * h * w, n, c, cout, h, w,
-                                        1 if clamp else 0, _stream())
-        if rc != 0:
-            raise RuntimeError("isrShuffleTailColour failed (%d)" % rc)
-        return out
+        f, fp, fi = _plane_strides(f)
+        g = g.contiguous()
+        gp, gi = 16 * h * w, cout * 16 * h * w
+        df = dw = db = None
+        if need[0]:
+            df = torch.empty((n, c, h, w), dtype=torch.float32, device=f.device)
+            rc = lib.isrShuffleTailDataGrad(_ptr(g), gp, gi, _ptr(weight.detach().contiguous()), _ptr(df), h * w, c * h * w, n, c, cout, h, w, _stream())
+            if rc != 0:
+                raise RuntimeError("isrShuffleTailDataGrad failed (%d)" % rc)
+        if need[1] or (ctx.has_bias and need[2]):
+            tiles = lib.isrShuffleTailGradTiles(n, h, w)
+            ws = torch.empty(tiles * cout * 37, dtype=torch.float64, device=f.device)
+            dw = torch.empty((cout, 4, 3, 3), dtype=torch.float32, device=f.device)
+            db = torch.empty(cout, dtype=torch.float32, device=f.device) if ctx.has_bias else None
+            rc = lib.isrShuffleTailWeightGrad(_ptr(g), gp, gi, _ptr(f), fp, fi, n, c, cout, h, w, tiles, _ptr(ws), _ptr(dw), _ptr(db), _stream())
+            if rc != 0:
+                raise RuntimeError("isrShuffleTailWeightGrad failed (%d)" % rc)
+        return df, dw if need[1] else None, db if (ctx.has_bias and need[2]) else None
 
 
 # ---- the viewer's display stage (viewer.py) --------------------------------------------------------------------------------------------

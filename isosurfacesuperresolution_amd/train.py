@@ -13,6 +13,9 @@ scheduler of ``:287-300``: Adam(lr 1e-4), ``StepLR(lrStep, 0.5)`` stepped at epo
         previous_output = cat(clamp(mask), normalize(normal), clamp(depth), clamp(ao))   # NOT detached
       loss.backward(); optimizer.step()
 
+``colour_clip_loss`` is the same loop for the colour networks (``mainVideo.py:381-434``: three output channels, the clamped
+prediction fed back, a criterion the caller brings); ``train_step`` and ``GraphedTrainStep`` take it as ``clip_loss=``.
+
 The reference has nothing distributed.  ``DataParallelTrainer`` adds the
 MI355X form: one process per GPU, the global batch split over ranks, identical initial weights
 (rank 0 broadcast), and after ``backward`` ONE all-reduce of a single flat 3.64 MB gradient bucket
@@ -98,6 +101,45 @@ def clip_loss(model, criterion, input, flow, target, initial_image="zero", upsca
         loss_sum = loss0.detach() if loss_sum is None else loss_sum + loss0.detach()
     if lazy_before is not None:
         criterion.lazy_values = lazy_before
+    return loss, loss_sum
+
+
+def colour_clip_loss(model, criterion, input, flow, target, upscale=4, disable_temporal=False):
+    """The clip recurrence of the reference's colour trainer (``SuperresolutionNetwork/mainVideo.py:381-434``, ``deferredShading``) for a
+    three-channel network such as ``models.RCAN``: input [B,T,C,h,w], flow [B,T,2,h,w], target [B,T,3,4h,4w] -> (loss tensor, sum of
+    the per-frame losses), as ``clip_loss`` without a host read-back.
+
+        j == 0 (or disable_temporal): previous_warped = zeros [B,3,4h,4w];  previous_warped_loss = target[:,0]          (:386, :395)
+        j  > 0: previous_warped = previous_warped_loss = warp_upscale(previous_output, flow[:,j-1], 4)                  (:407-408)
+        prediction = clamp(model(cat(input[:,j], flatten_high(previous_warped, 4)))[0], 0, 1)                           (:409-416)
+        loss += criterion(target[:,j], prediction, input[:,j], previous_warped_loss)[0]                                 (:418-422)
+        previous_output = prediction                                    # NOT detached: gradients flow through time     (:434)
+
+    ``criterion``: any callable with the signature of the reference's ``LossNet.forward`` -> (loss, values).  The reference's own
+    call of it is commented out in favour of two hard-wired MSE terms (:424-430), and ``losses.LossNet`` (VGG and GAN terms) is not
+    part of this package: the caller brings the criterion."""
+    B, T, Cout, Hh, Wh = target.shape
+    if ops.TRAIN_SPLIT and not ops.TRAIN_BF16 and target.is_cuda and torch.is_grad_enabled():
+        # every weight changed in the last optimizer step: refresh all split-kernel weight images in two launches
+        ops.prepare_split_many([m.weight for m in model.modules()
+                                if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.out_channels > 8 and m.in_channels > 8])
+    previous_output = None
+    loss = 0
+    loss_sum = None
+    for j in range(T):
+        if j == 0 or disable_temporal:
+            previous_warped = torch.zeros(B, Cout, Hh, Wh, dtype=input.dtype, device=input.device)
+            previous_warped_loss = target[:, 0]
+        else:
+            previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=False)
+            previous_warped_loss = previous_warped
+        single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
+        prediction, _ = model(single_input)
+        prediction = torch.clamp(prediction, 0, 1)
+        loss0, _ = criterion(target[:, j], prediction, input[:, j], previous_warped_loss)
+        loss = loss + loss0
+        loss_sum = loss0.detach() if loss_sum is None else loss_sum + loss0.detach()
+        previous_output = prediction
     return loss, loss_sum
 
 
@@ -254,11 +296,12 @@ def step_scheduler(optimizer, scheduler):
     return float(optimizer.param_groups[0]['lr'])
 
 
-def train_step(model, criterion, optimizer, batch, **kw):
-    """One optimisation step on a clip batch (single process)."""
+def train_step(model, criterion, optimizer, batch, clip_loss=None, **kw):
+    """One optimisation step on a clip batch (single process).  ``clip_loss``: the clip's recurrence -- this module's ``clip_loss``
+    (the unshaded networks) unless given, ``colour_clip_loss`` for a colour network; ``kw`` goes to it."""
     input, flow, target = batch
     optimizer.zero_grad()          # (FlatAdam: one zero_ of its flat gradient buffer, the views stay)
-    loss, loss_sum = clip_loss(model, criterion, input, flow, target, **kw)
+    loss, loss_sum = (clip_loss or globals()['clip_loss'])(model, criterion, input, flow, target, **kw)
     backward(loss)
     optimizer.step()
     return float(loss_sum.item()) / target.shape[1]
@@ -309,8 +352,9 @@ class GraphedTrainStep:
     (``ops.invalidate_weight_images``): inference or an eager step after a replay re-prepares them from the current
     weights.  The graph itself is unaffected: it refreshes its own image buffers at the start of every replay."""
 
-    def __init__(self, model, criterion, optimizer, example_batch, all_reduce=None, zero_grad=None, warmup=3, **kw):
+    def __init__(self, model, criterion, optimizer, example_batch, all_reduce=None, zero_grad=None, warmup=3, clip_loss=None, **kw):
         self.model, self.criterion, self.optimizer, self.kw = model, criterion, optimizer, kw
+        self.clip_loss = clip_loss or globals()['clip_loss']       # (``colour_clip_loss`` for a colour network; ``kw`` goes to it)
         self.all_reduce = all_reduce
         if zero_grad is None:
             zero_grad = self.optimizer.zero_grad if isinstance(self.optimizer, FlatAdam) else (lambda: self.optimizer.zero_grad(set_to_none=True))
@@ -342,7 +386,7 @@ class GraphedTrainStep:
     def _eager(self):
         input, flow, target = self.static
         self.zero_grad()
-        loss, loss_sum = clip_loss(self.model, self.criterion, input, flow, target, **self.kw)
+        loss, loss_sum = self.clip_loss(self.model, self.criterion, input, flow, target, **self.kw)
         backward(loss)
         if self.all_reduce is not None:
             self.all_reduce()
