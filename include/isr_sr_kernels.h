@@ -465,6 +465,25 @@ int isrConvTransposeDataGradPrepare(const float* w, void* wq, void* stream);
 int isrConvTranspose3x3S2DataGradSplitSupported(int N, int C, int h, int w);
 int isrConvTranspose3x3S2DataGradSplit(const float* G, const void* wq, float* gx, int N, int C, int h, int w, void* stream);
 
+/* STRIDE-2 3x3 convolution y = act(conv2d(x, w, bias, stride = 2, padding = 1)) (csrc/sr_conv_stride2.hip): the halving layers of the
+ * reference's discriminators (SuperresolutionNetwork/losses/enhancenetsmall.py, enhancenetlarge.py).  x [N][Cin][H][W], w [Cout][Cin][3][3]
+ * as nn.Conv2d holds it (no prepared image), y and gz [N][Cout][H/2][W/2], all packed fp32.  Exact fp32 MFMA, every sum in a fixed order
+ * (the same bits on every run); kernels take the caller's stream and allocate nothing.
+ *   ...Supported: H and W even, Cin and Cout multiples of 16 from 16 to 256 (else every entry point returns -3).
+ *   ...Forward: nine Cin x Cout products per output pixel, bias (may be NULL) and activation (ISR_ACT_NONE or ISR_ACT_LEAKY) in the epilogue.
+ *   ...DataGrad: gx[n][ci][p][q] = sum_{co, ky, kx : p = 2i + ky - 1, q = 2j + kx - 1} gz[n][co][i][j] w[co][ci][ky][kx], by output parity
+ *     (1, 2, 2 and 4 taps); gz is the gradient of the PRE-activation (isrActBackward first); gx 8-byte aligned.
+ *   ...WeightGradSegments: dw[Cout][Cin][3][3] and db[Cout] (may be NULL) summed over `segments` (<= isrConvWeightGradMaxSegments()) pairs
+ *     xs[k], gzs[k] (HOST arrays of device pointers), slabs of pixels reduced in slab order; workspace: ...WeightGradWorkspace(...) bytes.
+ * 0 ok, -1 bad arguments, -2 launch failure, -3 unsupported. */
+int isrConv3x3S2Supported(int N, int Cin, int Cout, int H, int W);
+int isrConv3x3S2Forward(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int H, int W, int Cout,
+                        int act, float slope, void* stream);
+int isrConv3x3S2DataGrad(const float* gz, const float* w, float* gx, int N, int Cin, int H, int W, int Cout, void* stream);
+long long isrConv3x3S2WeightGradWorkspace(int N, int Cin, int H, int W, int Cout);
+int isrConv3x3S2WeightGradSegments(const float* const* xs, const float* const* gzs, int segments, float* dw, float* db, void* workspace,
+                                   int N, int Cin, int H, int W, int Cout, void* stream);
+
 /* The DISPLAY STAGE of the viewer's frame in one launch (csrc/sr_display.hip), per high-resolution pixel: what the reference viewer does
  * between the network and the window (SuperresolutionNetwork/mainGUI.py:603-608,626-636,762-853) -- the twelve-channel image (x4
  * bilinear of the low G-buffer with the network's channels in place), background masking, the focus-of-context blend with a

@@ -13,10 +13,16 @@ static ``pad``) for the l1 / mse(l2) / temp-l2 terms of the README recipe
 * normals are re-normalised, the gt mask ``clamp(m/2+1/2, 0, 1)`` gates normal / ao / depth terms
   (``:236-256``); colours come from an internal shader with fov 30, light (0,0,1), white material,
   specular off, strengths from ``opt.lossAmbient / lossDiffuse / lossSpecular / lossAO`` (``:116-126``);
-* ``temp-l2`` compares against the warped previous prediction (``:357-388``).
+* ``temp-l2`` compares against the warped previous prediction (``:357-388``);
+* the adversarial terms ``adv`` / ``gan`` (spatio-temporal, 26 channels), ``tgan`` (temporal, 16) and ``sgan`` (spatial, 13), target
+  ``all`` (``:80-105``, ``:313-354``): each owns a discriminator built by ``LossBuilder.gan_loss(opt.discriminator, ...)`` and adds
+  ``weight * BCE-with-logits(discriminator(input), 1)`` to the generator's loss; ``train_discriminator`` (``:414-495``) is the
+  discriminators' own loss on a ground-truth and a predicted input.  The tensors fed to a discriminator (normalise, shade, pad,
+  concatenate) are assembled with torch operators; the networks run on ``ops.conv3x3`` / ``ops.conv3x3_s2``.
 
-Parity note: this module is checked against hand-derived values only -- importing the reference's
-``losses`` package needs torchvision, which this image lacks (parity unpinned for S7).
+Parity: the l1 / mse / temp-l2 terms are checked against hand-derived values; the adversarial terms, ``train_discriminator`` and the
+discriminators against values recorded from the reference's own modules (tests/golden/make_gan_fixtures.py, which supplies an empty
+stand-in for the ``torchvision`` import that only the VGG terms use).
 """
 import numpy as np
 import torch
@@ -29,9 +35,10 @@ from ..utils import ScreenSpaceShading
 
 class LossBuilder:
     """Factory of the elementary loss modules ``LossNetUnshaded`` is assembled from (``SuperresolutionNetwork/losses/lossbuilder.py``): the
-    terms of the hot-path training recipe (``l1``, ``mse``; README.md:45-64).  The reference's VGG perceptual / texture losses need a download
-    of VGG19 weights (``lossbuilder.py:10,173``) and the GAN losses are not part of the recipe: out of scope,
-    they raise."""
+    terms of the hot-path training recipe (``l1``, ``mse``; README.md:45-64) and the adversarial loss with the reference's two EnhanceNet
+    discriminators (``:232-258``, ``:306-331``).  The reference's VGG perceptual / texture losses need a download of VGG19 weights
+    (``lossbuilder.py:10,173``): out of scope, they raise; so do the TecoGAN discriminator and the
+    Wasserstein form."""
 
     def __init__(self, device):
         self.device = device
@@ -48,8 +55,57 @@ class LossBuilder:
     def downsample_loss(self, *a, **k):
         self._unsupported("downsample loss")
 
-    def gan_loss(self, *a, **k):
-        self._unsupported("adversarial loss")
+    class AdversarialLoss(nn.Module):
+        """``lossbuilder.py:232-258``: the non-saturating GAN loss on logits.  ``forward(x)``: the generator's loss, BCE of the
+        discriminator's logits for a prediction against the label TRUE.  ``train_discr``: the discriminator's loss, BCE of its logits for
+        the ground-truth input against TRUE plus for the predicted input against FAKE, and the mean sigmoid of both (floats, as the
+        reference returns them; detached tensors with ``lazy_values``, so that a step can be enqueued without a stall).  The labels are
+        float tensors: the reference's ``torch.full(shape, 1)`` was written when that gave the default float type."""
+        TRUE_LABEL = 1
+        FAKE_LABEL = 0
+
+        def __init__(self):
+            super().__init__()
+            self.lazy_values = False
+
+        @staticmethod
+        def _bce(logits, label):
+            return F.binary_cross_entropy_with_logits(logits, torch.full(logits.shape, float(label), dtype=logits.dtype, device=logits.device))
+
+        def forward(self, x):
+            return self._bce(x, LossBuilder.AdversarialLoss.TRUE_LABEL)
+
+        def train_discr(self, gt_input, pred_input, discr):
+            gt_logits = discr(gt_input)
+            pred_logits = discr(pred_input)
+            gt_score = torch.mean(torch.sigmoid(gt_logits)).detach()
+            pred_score = torch.mean(torch.sigmoid(pred_logits)).detach()
+            if not self.lazy_values:
+                gt_score, pred_score = gt_score.item(), pred_score.item()
+            loss = self._bce(gt_logits, LossBuilder.AdversarialLoss.TRUE_LABEL) + self._bce(pred_logits, LossBuilder.AdversarialLoss.FAKE_LABEL)
+            return loss, gt_score, pred_score
+
+    def build_discriminator(self, model, resolution, input_channels, additional_opt):
+        """``lossbuilder.py:306-322``: the discriminator named ``model`` (case-insensitive)."""
+        name = str(model).lower()
+        if name == 'enhancenetsmall':
+            from .enhancenetsmall import EnhanceNetSmallDiscriminator
+            return EnhanceNetSmallDiscriminator(resolution, input_channels)
+        if name == 'enhancenetlarge':
+            from .enhancenetlarge import EnhanceNetLargeDiscriminator
+            return EnhanceNetLargeDiscriminator(resolution, input_channels)
+        if name == 'tecogan':
+            raise NotImplementedError("the tecoGAN discriminator (4x4 convolutions, LeakyReLU slope 0.2) has no kernels in this package; "
+                                      "use enhanceNetSmall or enhanceNetLarge")
+        raise ValueError('Unsupported discriminator model: %s' % model)
+
+    def gan_loss(self, model, resolution, input_channels, additional_opt):
+        """``lossbuilder.py:324-331`` -> (discriminator, AdversarialLoss)."""
+        return self.build_discriminator(model, resolution, input_channels, additional_opt), LossBuilder.AdversarialLoss()
+
+    def wgan_loss(self, *a, **k):
+        # (the reference's own train_discr for it reads names it never defines, lossbuilder.py:284-296)
+        self._unsupported("the Wasserstein adversarial loss")
 
     def get_style_and_content_loss(self, *a, **k):
         self._unsupported("VGG perceptual/texture loss")
@@ -59,8 +115,9 @@ _TARGETS = ('mask', 'normal', 'color', 'ao', 'depth', 'all')
 
 
 class LossNetUnshaded(nn.Module):
-    # forward() accepts the upsampled low-resolution input and its warped predecessor like the reference's, but none of
-    # the supported terms reads them (only the adversarial ones would): train.clip_loss skips producing them
+    # forward() accepts the upsampled low-resolution input and its warped predecessor like the reference's; only the adversarial
+    # terms read them: train.clip_loss skips producing them for a criterion without a discriminator (an instance with one sets
+    # uses_input = True)
     uses_input = False
 
     def __init__(self, device, input_channels, output_channels, high_res, padding, opt):
@@ -100,7 +157,22 @@ class LossNetUnshaded(nn.Module):
                 loss_dict['temp-l2'] = builder.mse()
                 self.weight_dict[('temp-l2', target)] = weight
                 self.has_temporal_l2_loss = True
-            elif name in ('l2-ds', 'l1-ds', 'perceptual', 'texture', 'adv', 'gan', 'tgan', 'sgan'):
+            elif name in ('adv', 'gan', 'tgan', 'sgan'):
+                # (:80-105) spatio-temporal: input + previous input + prediction + previous prediction (5 + 5 + 8 + 8); temporal: the two
+                # predictions; spatial: input + prediction
+                assert target == 'all'
+                attr, key, channels = {'adv': ('', 'adv', 26), 'gan': ('', 'adv', 26), 'tgan': ('temp_', 'tgan', 16),
+                                       'sgan': ('spatial_', 'sgan', 13)}[name]
+                discr, adv = builder.gan_loss(opt.discriminator, high_res, channels, opt)
+                setattr(self, attr + 'discriminator', discr)
+                setattr(self, attr + 'adv_loss', adv)
+                self.weight_dict[(key, target)] = weight
+                if key == 'adv':
+                    self.discriminator_use_previous_image = True
+                    self.discriminator_clip_weights = False
+                self.has_discriminator = True
+                self.uses_input = True
+            elif name in ('l2-ds', 'l1-ds', 'perceptual', 'texture'):
                 raise NotImplementedError("loss '%s' is outside the accelerated hot path" % name)
             else:
                 raise ValueError('unknown loss %s' % name)
@@ -120,8 +192,22 @@ class LossNetUnshaded(nn.Module):
         self.shading = sh
         print('LossNet: ambient occlusion strength:', opt.lossAO)
 
+    _DISCRIMINATORS = ('discriminator', 'temp_discriminator', 'spatial_discriminator')
+
+    def discriminators(self):
+        """{attribute name: module} of the discriminators this criterion owns (none without an adversarial term)."""
+        return {name: getattr(self, name) for name in self._DISCRIMINATORS if hasattr(self, name)}
+
     def get_discr_parameters(self):
-        return []
+        return [p for d in self.discriminators().values() for p in d.parameters()]
+
+    def discr_eval(self):
+        for d in self.discriminators().values():
+            d.eval()
+
+    def discr_train(self):
+        for d in self.discriminators().values():
+            d.train()
 
     @staticmethod
     def pad(img, border):
@@ -141,10 +227,11 @@ class LossNetUnshaded(nn.Module):
                 and (prev is None or (prev.is_cuda and prev.dtype == torch.float32 and prev.shape == pred.shape)))
 
     def _forward_fused(self, gt, pred, prev):
+        fused_weights = {k: v for k, v in self.weight_dict.items() if k[0] in ops.LOSS_KINDS}       # (the adversarial terms are added by forward)
         key = (tuple(self.shading.packed_parameters()), self.shading._ao, bool(self.shading.inverse_ao), self.padding,
-               tuple(sorted(self.weight_dict.items())))
+               tuple(sorted(fused_weights.items())))
         if self._fused_cfg[0] != key:
-            self._fused_cfg = (key, ops.loss_unshaded_config(self.weight_dict, self.padding, self.shading))
+            self._fused_cfg = (key, ops.loss_unshaded_config(fused_weights, self.padding, self.shading))
         vals = ops.loss_unshaded(gt, pred, prev if self.has_temporal_l2_loss else None, self._fused_cfg[1])
         host = None if self.lazy_values else vals.detach().tolist()
         values = {}
@@ -160,7 +247,15 @@ class LossNetUnshaded(nn.Module):
         assert Cout == 6
         assert gt.shape == pred.shape
         if self._fusable(gt, pred, prev_pred_warped):
-            return self._forward_fused(gt, pred, prev_pred_warped)
+            # the fused launch computes the l1 / mse / temp-l2 part; the adversarial terms are added to its total
+            total, values = self._forward_fused(gt, pred, prev_pred_warped)
+            if self.has_discriminator:
+                pred_pad = LossNetUnshaded.pad(pred, self.padding)
+                adv, adv_values = self._adversarial_terms(pred_pad, self.shading(pred_pad), input, prev_input_warped,
+                                                          LossNetUnshaded.pad(prev_pred_warped, self.padding))
+                total = total + adv
+                values.update(adv_values)
+            return total, values
         gt = LossNetUnshaded.pad(gt, self.padding)
         pred = LossNetUnshaded.pad(pred, self.padding)
         if prev_pred_warped is not None:
@@ -190,6 +285,11 @@ class LossNetUnshaded(nn.Module):
                     values[key] = loss.detach() if self.lazy_values else loss.item()
                     total = total + self.weight_dict[key] * loss
 
+        if self.has_discriminator:
+            adv, adv_values = self._adversarial_terms(pred, pred_color, input, prev_input_warped, prev_pred_warped)
+            total = total + adv
+            values.update(adv_values)
+
         if self.has_temporal_l2_loss:
             crit = self.loss_dict['temp-l2']
             prev = prev_pred_warped
@@ -208,3 +308,60 @@ class LossNetUnshaded(nn.Module):
                     values[key] = loss.detach() if self.lazy_values else loss.item()
                     total = total + self.weight_dict[key] * loss
         return total, values
+
+    def _adversarial_terms(self, pred, pred_color, input, prev_input_warped, prev_pred_warped):
+        """The generator's adversarial terms (``:313-354``) -> (weighted sum, {'discr_pred' | 'temp_discr_pred' | 'spatial_discr_pred': value}).
+        ``pred`` and ``prev_pred_warped`` arrive with their border already zeroed and ``pred_color`` is the shading of that ``pred``: the
+        reference pads, then normalises and shades, then pads AGAIN (``:205-208``, ``:333-336``) -- a zeroed normal shades to the ambient
+        term, which the second padding removes."""
+        if input is None or prev_input_warped is None or prev_pred_warped is None:
+            raise ValueError("the adversarial terms need the upsampled input, the warped previous input and the warped previous prediction")
+        norm = ScreenSpaceShading.normalize
+        # generator side: mask, normal, COLOUR, ao (:315-319, :322-331) -- train_discriminator below orders ao before colour
+        pred_with_color = torch.cat([pred[:, 0:1], norm(pred[:, 1:4], dim=1), pred_color, pred[:, 5:6]], dim=1)
+        prev_normal = norm(prev_pred_warped[:, 1:4], dim=1)
+        prev_color = self.shading(torch.cat([prev_pred_warped[:, 0:1], prev_normal, prev_pred_warped[:, 4:6]], dim=1))
+        prev_with_color = torch.cat([prev_pred_warped[:, 0:1], prev_normal, prev_color, prev_pred_warped[:, 5:6]], dim=1)
+        pad = LossNetUnshaded.pad
+        input_pad, prev_input_pad = pad(input, self.padding), pad(prev_input_warped, self.padding)
+        pred_pad, prev_pad = pad(pred_with_color, self.padding), pad(prev_with_color, self.padding)
+        total, values = 0.0, {}
+        for key, value_key, attr, parts in (('adv', 'discr_pred', '', (input_pad, prev_input_pad, pred_pad, prev_pad)),
+                                            ('tgan', 'temp_discr_pred', 'temp_', (pred_pad, prev_pad)),
+                                            ('sgan', 'spatial_discr_pred', 'spatial_', (input_pad, pred_pad))):
+            if (key, 'all') in self.weight_dict:
+                loss = getattr(self, attr + 'adv_loss')(getattr(self, attr + 'discriminator')(torch.cat(parts, dim=1)))
+                values[value_key] = loss.detach() if self.lazy_values else loss.item()
+                total = total + self.weight_dict[(key, 'all')] * loss
+        return total, values
+
+    def train_discriminator(self, input, gt_high, previous_input, gt_prev_warped, pred_high, pred_prev_warped):
+        """The discriminators' loss for one frame (``:414-495``), everything at high resolution: ``input`` and ``previous_input``
+        [B, 5, H, W] (mask, normal, depth), the other four [B, 6, H, W] -> (loss, gt score, pred score), each the weighted sum over the
+        adversarial terms of ``AdversarialLoss.train_discr`` on a ground-truth and a predicted input."""
+        assert self.has_discriminator
+        norm = ScreenSpaceShading.normalize
+
+        def colorize_and_pad(t):
+            assert t.shape[1] == 6
+            mask, normal, ao = t[:, 0:1], norm(t[:, 1:4], dim=1), t[:, 5:6]
+            color = self.shading(torch.cat([mask, normal, t[:, 4:6]], dim=1))
+            # discriminator side: mask, normal, AO, colour (:436) -- the generator side above orders colour before ao
+            return LossNetUnshaded.pad(torch.cat([mask, normal, ao, color], dim=1), self.padding)
+
+        input = LossNetUnshaded.pad(input, self.padding)
+        previous_input = LossNetUnshaded.pad(previous_input, self.padding)
+        gt_high, pred_high = colorize_and_pad(gt_high), colorize_and_pad(pred_high)
+        gt_prev_warped, pred_prev_warped = colorize_and_pad(gt_prev_warped), colorize_and_pad(pred_prev_warped)
+        discr_loss = gt_score = pred_score = 0
+        for key, attr, gt_parts, pred_parts in (
+                ('adv', '', (input, previous_input, gt_high, gt_prev_warped), (input, previous_input, pred_high, pred_prev_warped)),
+                ('tgan', 'temp_', (gt_high, gt_prev_warped), (pred_high, pred_prev_warped)),
+                ('sgan', 'spatial_', (input, gt_high), (input, pred_high))):
+            if (key, 'all') in self.weight_dict:
+                adv = getattr(self, attr + 'adv_loss')
+                adv.lazy_values = self.lazy_values
+                loss0, gt0, pred0 = adv.train_discr(torch.cat(gt_parts, dim=1), torch.cat(pred_parts, dim=1), getattr(self, attr + 'discriminator'))
+                w = self.weight_dict[(key, 'all')]
+                discr_loss, gt_score, pred_score = discr_loss + w * loss0, gt_score + w * gt0, pred_score + w * pred0
+        return discr_loss, gt_score, pred_score

@@ -185,6 +185,13 @@ def _bind(lib):
         lib.isrConvTransposeDataGradPrepare.argtypes = [vp, vp, vp]; lib.isrConvTransposeDataGradPrepare.restype = ci
         lib.isrConvTranspose3x3S2DataGradSplitSupported.argtypes = [ci, ci, ci, ci]; lib.isrConvTranspose3x3S2DataGradSplitSupported.restype = ci
         lib.isrConvTranspose3x3S2DataGradSplit.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]; lib.isrConvTranspose3x3S2DataGradSplit.restype = ci
+    if hasattr(lib, "isrConv3x3S2Forward"):                     # (likewise: the stride-2 convolution, csrc/sr_conv_stride2.hip)
+        lib.isrConv3x3S2Supported.argtypes = [ci, ci, ci, ci, ci]; lib.isrConv3x3S2Supported.restype = ci
+        lib.isrConv3x3S2Forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]; lib.isrConv3x3S2Forward.restype = ci
+        lib.isrConv3x3S2DataGrad.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]; lib.isrConv3x3S2DataGrad.restype = ci
+        lib.isrConv3x3S2WeightGradWorkspace.argtypes = [ci, ci, ci, ci, ci]; lib.isrConv3x3S2WeightGradWorkspace.restype = ll
+        lib.isrConv3x3S2WeightGradSegments.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+        lib.isrConv3x3S2WeightGradSegments.restype = ci
     if hasattr(lib, "isrChannelGateScaleAdd"):                  # (likewise: RCAN's channel attention and pixel-shuffle tail, csrc/sr_attention.hip)
         lib.isrChannelPoolSlabs.argtypes = [ci, ci, ci]; lib.isrChannelPoolSlabs.restype = ci
         lib.isrChannelPoolSupported.argtypes = [ci, ci, ci, ci, ll, ll]; lib.isrChannelPoolSupported.restype = ci
@@ -407,7 +414,9 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  39: "channel_pool_kernel", 40: "gate_scale_add_kernel", 41: "shuffle_tail_kernel",
                  # ... and their backward
                  42: "gate_grad_sum_kernel", 43: "gate_backward_kernel", 44: "gate_param_grad_kernel",
-                 45: "shuffle_tail_dgrad_kernel", 46: "shuffle_tail_wgrad_kernel", 47: "shuffle_tail_wgrad_sum_kernel"}
+                 45: "shuffle_tail_dgrad_kernel", 46: "shuffle_tail_wgrad_kernel", 47: "shuffle_tail_wgrad_sum_kernel",
+                 # the stride-2 convolution of the discriminators (csrc/sr_conv_stride2.hip)
+                 48: "conv3x3s2_fwd_kernel", 49: "conv3x3s2_dgrad_kernel", 50: "conv3x3s2_wgrad_kernel", 51: "conv3x3s2_wgrad_sum_kernel"}
 
 
 def debug_switches():
@@ -1047,7 +1056,9 @@ class deferred_weight_gradients:
         if exc_type is not None:
             return False
         for key, (weight, bias, xs, gzs) in pending.items():
-            if len(key) > 2:         # a transposed convolution: (x, phase-major gradient) pairs, the gradient gathered into its own layout
+            if len(key) > 2 and key[2] == "s2":      # a stride-2 convolution: its own weight-gradient kernel
+                gw, gb = _conv_s2_weight_grad(xs, gzs, weight, bias is not None)
+            elif len(key) > 2:       # a transposed convolution: (x, phase-major gradient) pairs, the gradient gathered into its own layout
                 gw, gb = _convt_weight_grad(xs, gzs, weight, bias is not None)
             elif _weight_grad_into_grad(xs, gzs, weight, bias):
                 continue
@@ -1096,9 +1107,10 @@ def _has_grad_hooks(p):
     return p is not None and bool(getattr(p, '_backward_hooks', None) or getattr(p, '_post_accumulate_grad_hooks', None))
 
 
-def _weight_grad_or_defer(weight, bias, has_bias, x, gz, convt=False):
+def _weight_grad_or_defer(weight, bias, has_bias, x, gz, convt=False, s2=False):
     """Inside deferred_weight_gradients(): record the pair and return (None, None); else compute (dw, db) now.
     ``convt``: ``weight`` is a ConvTranspose2d weight [ci, co, 3, 3] and ``gz`` the phase-major gradient (``_convt_weight_grad``).
+    ``s2``: the layer is a stride-2 convolution, ``gz`` has half of x's size (``_conv_s2_weight_grad``).
 
     Deferred gradients are written to ``param.grad`` when the context exits, AFTER ``loss.backward()`` and without
     passing through autograd's accumulation: tensor hooks and post-accumulate-grad hooks (DDP-style reducers,
@@ -1107,12 +1119,12 @@ def _weight_grad_or_defer(weight, bias, has_bias, x, gz, convt=False):
     through autograd as usual); ``torch.autograd.grad`` on convolution weights must be called outside the context."""
     if _deferred is not None and weight.is_leaf and (bias is None or bias.is_leaf) \
             and not _has_grad_hooks(weight) and not _has_grad_hooks(bias):
-        key = (id(weight), tuple(x.shape), "convt") if convt else (id(weight), tuple(x.shape))
+        key = (id(weight), tuple(x.shape), "convt") if convt else (id(weight), tuple(x.shape), "s2") if s2 else (id(weight), tuple(x.shape))
         entry = _deferred.setdefault(key, (weight, bias, [], []))
         entry[2].append(x)
         entry[3].append(gz)
         return None, None
-    return (_convt_weight_grad if convt else _weight_grad)([x], [gz], weight, has_bias)
+    return (_convt_weight_grad if convt else _conv_s2_weight_grad if s2 else _weight_grad)([x], [gz], weight, has_bias)
 
 
 # A residual block of a batch of SMALL images (the 32 x 32 training crops: too few 8 x 32 tiles for the streaming kernel) as ONE
@@ -1721,6 +1733,157 @@ def conv_transpose3x3_s2(x, weight, bias=None, act='none', slope=0.01):
     if hot_in:
         y._isr_range_key = HOT          # whatever consumes it stays exact too (its range is not tracked)
     return y
+
+
+# ---- stride-2 convolution: the halving layers of the discriminators (csrc/sr_conv_stride2.hip) -------------------------------------
+# Route of ``conv3x3_s2`` on device tensors: "kernel" -- the dedicated forward, data-gradient and weight-gradient kernels; "embedded" --
+# the layer as a stride-1 3x3 layer over ``F.pixel_unshuffle(x, 2)`` with 9 of its 36 taps live, on ``conv3x3`` (4x the matrix work: the
+# form a layer takes before it has a kernel); "torch" -- PyTorch's own convolution.  The last two are what tools/bench_gan_train.py
+# measures the kernels against.
+CONV_S2_ROUTE = os.environ.get("ISR_CONV_S2_ROUTE", "kernel")
+_CONV_S2_TAPS = ((1, 0), (0, 1), (1, 1))                        # tap k -> (phase bit, embedded row / column): input row 2i + k - 1 = 2 (i + r - 1) + a
+
+
+def conv_s2_phase_weight(weight):
+    """The stride-2 convolution as a stride-1 3x3 convolution over ``F.pixel_unshuffle(x, 2)`` (channel 4 ci + 2 a + b = x[ci] at rows
+    2u + a, columns 2v + b): [co][4 ci + 2 a + b][r][s] holds w[co][ci][ky][kx] at (a, r) = (1, 0), (0, 1), (1, 1) for ky = 0, 1, 2, columns
+    alike, and zeros elsewhere.  Differentiable in ``weight``; no arithmetic: the same products, 27 of 36 taps structural zeros."""
+    cout, cin = weight.shape[0], weight.shape[1]
+    e = weight.new_zeros((cout, cin, 4, 3, 3))
+    for ky, (a, r) in enumerate(_CONV_S2_TAPS):
+        for kx, (b, q) in enumerate(_CONV_S2_TAPS):
+            e[:, :, 2 * a + b, r, q] = weight[:, :, ky, kx]
+    return e.reshape(cout, 4 * cin, 3, 3)
+
+
+def conv_s2_supported(x, weight):
+    """Do the stride-2 kernels take this layer?  Even sizes, channel counts that are multiples of 16 from 16 to 256."""
+    lib = _sr()
+    n, cin, h, w = x.shape
+    return hasattr(lib, "isrConv3x3S2Forward") and bool(lib.isrConv3x3S2Supported(n, cin, weight.shape[0], h, w))
+
+
+def _conv_s2_forward(x, weight, bias, act, slope):
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    _tally("exact", 2.0 * 9 * cin * cout * n * (h // 2) * (w // 2))
+    y = torch.empty((n, cout, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    wd = weight.detach().contiguous()
+    b = bias.detach().contiguous() if bias is not None else None
+    rc = _sr().isrConv3x3S2Forward(_ptr(x), _ptr(wd), _ptr(b), _ptr(y), n, cin, h, w, cout, ACT_CODES[act], float(slope), _stream())
+    if rc != 0:
+        raise RuntimeError("isrConv3x3S2Forward failed (%d)" % rc)
+    return y
+
+
+def _conv_s2_data_grad(gz, weight, h, w):
+    """gx [N, Cin, h, w] from the pre-activation gradient gz [N, Cout, h/2, w/2] (``isrConv3x3S2DataGrad``)."""
+    n, cout = gz.shape[0], gz.shape[1]
+    cin = weight.shape[1]
+    _tally("exact", 2.0 * 9 * cin * cout * n * (h // 2) * (w // 2))
+    gx = torch.empty((n, cin, h, w), dtype=torch.float32, device=gz.device)
+    rc = _sr().isrConv3x3S2DataGrad(_ptr(gz), _ptr(weight.detach().contiguous()), _ptr(gx), n, cin, h, w, cout, _stream())
+    if rc != 0:
+        raise RuntimeError("isrConv3x3S2DataGrad failed (%d)" % rc)
+    return gx
+
+
+def _conv_s2_weight_grad(xs, gzs, weight, has_bias):
+    """(dw, db) of a stride-2 convolution summed over the pairs (xs[k] [N, Cin, h, w], gzs[k] [N, Cout, h/2, w/2]) --
+    ``isrConv3x3S2WeightGradSegments``, one pass per <= 32 pairs."""
+    lib = _sr()
+    most = lib.isrConvWeightGradMaxSegments()
+    cout, cin = weight.shape[0], weight.shape[1]
+    n, _, h, w = xs[0].shape
+    ws = _wgrad_workspace(weight.device, lib.isrConv3x3S2WeightGradWorkspace(n * min(len(xs), most), cin, h, w, cout))
+    gw = gb = None
+    for k in range(0, len(xs), most):
+        px = [t.contiguous() for t in xs[k:k + most]]
+        pg = [t.contiguous() for t in gzs[k:k + most]]
+        dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+        db = torch.empty(cout, dtype=torch.float32, device=weight.device) if has_bias else None
+        _tally("exact", 2.0 * 9 * cin * cout * n * len(px) * (h // 2) * (w // 2))
+        rc = lib.isrConv3x3S2WeightGradSegments((ctypes.c_void_p * len(px))(*[t.data_ptr() for t in px]),
+                                                (ctypes.c_void_p * len(pg))(*[t.data_ptr() for t in pg]), len(px), _ptr(dw), _ptr(db),
+                                                _ptr(ws), n, cin, h, w, cout, _stream())
+        if rc != 0:
+            raise RuntimeError("isrConv3x3S2WeightGradSegments failed (%d)" % rc)
+        gw = dw if gw is None else gw + dw
+        gb = db if gb is None or db is None else gb + db
+    return gw, gb
+
+
+class _Conv3x3S2Function(torch.autograd.Function):
+    """y = act(conv2d(x, w, b, stride=2, padding=1)) as ONE autograd node on the stride-2 kernels: forward ``isrConv3x3S2Forward``;
+    backward ``isrActBackward`` on the saved output, ``isrConv3x3S2DataGrad`` (only when the input needs a gradient) and the weight
+    gradient through ``_weight_grad_or_defer`` (``isrConv3x3S2WeightGradSegments``, deferred over the frames of a clip)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, slope):
+        x = x.contiguous()
+        y = _conv_s2_forward(x, weight, bias, act, slope)
+        ctx.act, ctx.slope = act, slope
+        ctx.has_bias = bias is not None
+        ctx.bias = bias if (bias is not None and bias.requires_grad) else None
+        ctx.weight = weight
+        ctx.save_for_backward(x, y if act != 'none' else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y = ctx.saved_tensors
+        weight = ctx.weight
+        gy = gy.contiguous()
+        if ctx.act != 'none':
+            gz = torch.empty_like(gy)
+            rc = _sr().isrActBackward(_ptr(gy), _ptr(y), _ptr(gz), gy.numel(), ACT_CODES[ctx.act], float(ctx.slope), _stream())
+            if rc != 0:
+                raise RuntimeError("isrActBackward failed (%d)" % rc)
+        else:
+            gz = gy
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = _conv_s2_data_grad(gz, weight, x.shape[2], x.shape[3])
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw, gb = _weight_grad_or_defer(weight, ctx.bias, ctx.has_bias, x, gz, s2=True)
+        return gx, gw, gb, None, None
+
+
+def conv3x3_s2(x, weight, bias=None, act='none', slope=0.01):
+    """y = act(conv2d(x, w, bias, stride=2, padding=1)): x [N, Cin, H, W], weight [Cout, Cin, 3, 3] -> [N, Cout, H/2, W/2]; ``act`` is
+    'none' or 'leaky'.  The halving layers of the discriminators (losses/enhancenetsmall.py, enhancenetlarge.py).
+
+    * CPU tensors: ``F.conv2d`` and the activation.
+    * device fp32 tensors, no gradient needed: the forward kernel ``isrConv3x3S2Forward`` (exact fp32 MFMA, nine products per pixel).
+    * under autograd: ``_Conv3x3S2Function`` -- that forward, ``isrActBackward``, ``isrConv3x3S2DataGrad`` when the input needs a
+      gradient, and the weight gradient (``isrConv3x3S2WeightGradSegments``) deferred inside ``deferred_weight_gradients()`` like
+      every other layer's.
+    * ``CONV_S2_ROUTE``: "embedded" runs the layer as ``conv3x3`` over the pixel-unshuffled input, "torch" on PyTorch's convolution.
+    * odd sizes, channel counts that are no multiple of 16 or exceed 256: PyTorch's convolution (a warning says so, once)."""
+    if act not in ('none', 'leaky'):
+        raise ValueError("conv3x3_s2: activation 'none' or 'leaky' expected, not %r" % (act,))
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != weight.shape[1]:
+        raise ValueError("conv3x3_s2: x [N, Cin, H, W] and weight [Cout, Cin, 3, 3] expected")
+    if not x.is_cuda:
+        return _act_cpu(F.conv2d(x, weight, bias, stride=2, padding=1), act, slope)
+    if x.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise TypeError("conv3x3_s2 (HIP) computes in fp32")
+    if CONV_S2_ROUTE not in ("kernel", "embedded", "torch"):
+        raise ValueError("ops.CONV_S2_ROUTE: 'kernel', 'embedded' or 'torch' expected, not %r" % (CONV_S2_ROUTE,))
+    if CONV_S2_ROUTE == "torch":
+        return _act_cpu(F.conv2d(x, weight, bias, stride=2, padding=1), act, slope)
+    if x.shape[2] % 2 or x.shape[3] % 2 or (CONV_S2_ROUTE == "kernel" and not conv_s2_supported(x, weight)):
+        if CONV_S2_ROUTE == "kernel" and not hasattr(_sr(), "isrConv3x3S2Forward"):
+            raise RuntimeError("conv3x3_s2: the loaded kernel library has no stride-2 convolution (isrConv3x3S2Forward)")
+        _warn_once("conv_s2_shape", "conv3x3_s2: %d -> %d channels at %d x %d runs on PyTorch's own convolution (the HIP kernels take even "
+                   "sizes and channel counts that are multiples of 16 up to 256)" % (x.shape[1], weight.shape[0], x.shape[2], x.shape[3]))
+        return _act_cpu(F.conv2d(x, weight, bias, stride=2, padding=1), act, slope)
+    if CONV_S2_ROUTE == "embedded":
+        return conv3x3(F.pixel_unshuffle(x, 2), conv_s2_phase_weight(weight), bias, act=act, slope=slope)
+    needs_grad = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
+    if needs_grad:
+        return _Conv3x3S2Function.apply(x, weight, bias, act, slope)
+    return _conv_s2_forward(x.contiguous(), weight, bias, act, slope)
 
 
 # ---- training-side elementwise kernels (csrc/sr_train.hip) ---------------------------------------

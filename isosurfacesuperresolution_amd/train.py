@@ -13,6 +13,10 @@ scheduler of ``:287-300``: Adam(lr 1e-4), ``StepLR(lrStep, 0.5)`` stepped at epo
         previous_output = cat(clamp(mask), normalize(normal), clamp(depth), clamp(ao))   # NOT detached
       loss.backward(); optimizer.step()
 
+``adversarial_step`` / ``fit_adversarial`` restate the reference's second training mode, ``trainAdv_v2`` (``:475-636``), which it
+enters as soon as ``--losses`` names an adversarial term (``:296-312``): per batch the discriminators are trained on the generator's
+frozen predictions, then the generator against the discriminators.
+
 ``colour_clip_loss`` is the same loop for the colour networks (``mainVideo.py:381-434``: three output channels, the clamped
 prediction fed back, a criterion the caller brings); ``train_step`` and ``GraphedTrainStep`` take it as ``clip_loss=``.
 
@@ -66,8 +70,8 @@ def clip_loss(model, criterion, input, flow, target, initial_image="zero", upsca
         criterion.lazy_values = True
     kw = dict(mode=upsample, **({"align_corners": False} if upsample in ("bilinear", "bicubic") else {}))
     # the reference upsamples (and warps) the low-resolution inputs for every frame and hands them to the criterion
-    # (mainVideoUnshaded.py:432-452); LossNetUnshaded never reads them (only the GAN terms would), so a criterion
-    # that says so (uses_input = False) is not fed
+    # (mainVideoUnshaded.py:432-452); only LossNetUnshaded's adversarial terms read them, so a criterion without a
+    # discriminator says so (uses_input = False) and is not fed
     feed_inputs = getattr(criterion, 'uses_input', True)
     previous_input = input_high = None
     for j in range(T):
@@ -305,6 +309,168 @@ def train_step(model, criterion, optimizer, batch, clip_loss=None, **kw):
     backward(loss)
     optimizer.step()
     return float(loss_sum.item()) / target.shape[1]
+
+
+def make_adversarial_optimizers(model, criterion, lr=1e-4, lr_step=500, lr_gamma=0.5):
+    """The two optimizers of mainVideoUnshaded.py:303-312: Adam(lr) on the generator, Adam(lr * 0.5) on the discriminators' trainable
+    parameters, StepLR(lr_step, lr_gamma) on both -> (gen_optimizer, discr_optimizer, gen_scheduler, discr_scheduler)."""
+    discr_params = [p for p in criterion.get_discr_parameters() if p.requires_grad]
+    if not discr_params:
+        raise ValueError("make_adversarial_optimizers: the criterion has no discriminator (no adv / gan / tgan / sgan term in its losses)")
+    gen_optimizer = torch.optim.Adam(list(model.parameters()), lr=lr)
+    discr_optimizer = torch.optim.Adam(discr_params, lr=lr * 0.5)
+    return (gen_optimizer, discr_optimizer, torch.optim.lr_scheduler.StepLR(gen_optimizer, lr_step, lr_gamma),
+            torch.optim.lr_scheduler.StepLR(discr_optimizer, lr_step, lr_gamma))
+
+
+def discriminator_clip_loss(model, criterion, input, flow, target, initial_image="zero", upscale=4, upsample="bilinear",
+                            disable_temporal=False):
+    """The discriminator phase's loop over the frames of a clip (mainVideoUnshaded.py:511-566): the generator runs without gradients,
+    ``criterion.train_discriminator`` compares each frame's prediction with the ground truth -> (loss tensor, sum of the gt scores, sum
+    of the pred scores; device tensors, nothing is read back)."""
+    B, T, Cout, Hh, Wh = target.shape
+    kw = dict(mode=upsample, **({"align_corners": False} if upsample in ("bilinear", "bicubic") else {}))
+    lazy_before = criterion.lazy_values
+    criterion.lazy_values = True
+    loss, gt_sum, pred_sum, previous_output = 0, 0, 0, None
+    try:
+        for j in range(T):
+            if j == 0 or disable_temporal:
+                previous_warped = initialImage(input[:, 0], Cout, initial_image, False, upscale)
+                previous_warped_loss = target[:, 0]
+                previous_input = F.interpolate(input[:, 0], size=(Hh, Wh), **kw)
+            else:
+                previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=True)
+                previous_warped_loss = previous_warped
+                previous_input = VideoTools.warp_upscale(F.interpolate(input[:, j - 1], size=(Hh, Wh), **kw), flow[:, j - 1], upscale,
+                                                         special_mask=True)
+            single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
+            with torch.no_grad():
+                prediction, _ = model(single_input)
+            # at j = 0 this is frame -1 of the clip, the LAST one, warped by flow[:, -1] (mainVideoUnshaded.py:543-547 index with j - 1)
+            gt_prev_warped = VideoTools.warp_upscale(target[:, j - 1], flow[:, j - 1], upscale, special_mask=True)
+            input_high = F.interpolate(input[:, j], size=(Hh, Wh), **kw)
+            loss0, gt_score, pred_score = criterion.train_discriminator(input_high, target[:, j], previous_input, gt_prev_warped,
+                                                                        prediction, previous_warped_loss)
+            loss, gt_sum, pred_sum = loss + loss0, gt_sum + gt_score, pred_sum + pred_score
+            previous_output = torch.cat([torch.clamp(prediction[:, 0:1], -1, +1),
+                                         ScreenSpaceShading.normalize(prediction[:, 1:4], dim=1),
+                                         torch.clamp(prediction[:, 4:5], 0, +1),
+                                         torch.clamp(prediction[:, 5:6], 0, +1)], dim=1)
+    finally:
+        criterion.lazy_values = lazy_before
+    return loss, gt_sum, pred_sum
+
+
+def adversarial_step(model, criterion, gen_optimizer, discr_optimizer, batch, disc_steps=2, **kw):
+    """The body of ``trainAdv_v2`` for one batch (mainVideoUnshaded.py:506-624) -> (discr_loss, gen_loss, gt_score, pred_score): the
+    clip's loss of the LAST discriminator step and of the LAST generator step, and the discriminators' scores summed over every
+    discriminator step and frame, which is what the reference adds to its epoch totals (:567, :562-563, :621).
+
+    Discriminator phase, ``disc_steps`` times: the generator under ``no_grad``, ``discriminator_clip_loss``, one step of
+    ``discr_optimizer``.  Generator phase, ALSO ``disc_steps`` times (the reference's loop reads ``disc_steps``, not its
+    ``advGenMaxSteps``, :572): ``clip_loss`` with the adversarial terms, one step of ``gen_optimizer``.  There the discriminators'
+    parameters are switched to ``requires_grad_(False)`` and back: the reference computes their gradients and zeroes them unused
+    (:508-509, :573-574), so every parameter ends the same.  Both phases go through ``backward`` (deferred weight gradients);
+    ``kw`` goes to the two clip loops (initial_image, upscale, upsample, disable_temporal)."""
+    input, flow, target = batch
+    dkw = {k: v for k, v in kw.items() if k != "fused_recurrence"}
+    discr_loss = gen_loss = None
+    gt_score = pred_score = 0
+    for _ in range(disc_steps):
+        discr_optimizer.zero_grad()
+        gen_optimizer.zero_grad()
+        loss, gt_sum, pred_sum = discriminator_clip_loss(model, criterion, input, flow, target, **dkw)
+        backward(loss)
+        discr_optimizer.step()
+        discr_loss, gt_score, pred_score = loss.detach(), gt_score + gt_sum, pred_score + pred_sum
+    discr_params = [p for p in criterion.get_discr_parameters() if p.requires_grad]
+    for p in discr_params:
+        p.requires_grad_(False)
+    try:
+        for _ in range(disc_steps):
+            discr_optimizer.zero_grad()
+            gen_optimizer.zero_grad()
+            loss, _ = clip_loss(model, criterion, input, flow, target, **kw)
+            backward(loss)
+            gen_optimizer.step()
+            gen_loss = loss.detach()
+    finally:
+        for p in discr_params:
+            p.requires_grad_(True)
+    return tuple(float(v) for v in (discr_loss, gen_loss, gt_score, pred_score))       # (the step's read-back)
+
+
+DISCRIMINATOR_KEYS = ('discriminator', 'temp_discriminator', 'spatial_discriminator')
+
+
+def save_adversarial_checkpoint(modeldir, epoch, model, parameters, criterion, gen_optimizer, discr_optimizer, gen_scheduler, discr_scheduler):
+    """``checkpoint(epoch)`` of mainVideoUnshaded.py:799-811 in its adversarial branch: ``save_checkpoint``'s 'epoch', 'model' and
+    'parameters', the two optimizer and the two scheduler objects, and each discriminator's ``state_dict`` under its attribute name --
+    ``--pretrainedDiscr`` and the reference's restore read ``checkpoint['discriminator']`` (:326, :367).  The whole criterion object of
+    :809 is NOT written: the reference never reads it back, and it would need new names in the restricted unpickler."""
+    os.makedirs(modeldir, exist_ok=True)
+    path = checkpoint_path(modeldir, epoch)
+    opt_dict = dict(parameters) if isinstance(parameters, dict) else dict(vars(parameters))
+    state = {'epoch': epoch + 1, 'model': model, 'parameters': opt_dict, 'gen_optimizer': gen_optimizer, 'discr_optimizer': discr_optimizer,
+             'gen_scheduler': gen_scheduler, 'discr_scheduler': discr_scheduler}
+    state.update({name: d.state_dict() for name, d in criterion.discriminators().items()})
+    torch.save(state, path)
+    return path
+
+
+def fit_adversarial(model, criterion, train_loader, test_loader, modeldir, n_epochs, parameters, device=None, lr=1e-4, lr_step=500,
+                    lr_gamma=0.5, disc_steps=2, disc_initial_steps=None, restore=False, restore_epoch=-1, log=print, **kw):
+    """The epoch loop of mainVideoUnshaded.py:827-835 for a criterion with adversarial terms:
+
+        for epoch in range(start, n_epochs + 1):  trainAdv_v2(epoch); test(epoch); checkpoint(epoch)
+
+    ``trainAdv_v2`` (:475-636) = both schedulers stepped at the epoch's start, then ``adversarial_step`` per batch with
+    ``disc_initial_steps`` discriminator steps in epoch 1 if given, ``disc_steps`` otherwise (``--advDiscrInitialSteps``,
+    ``--advDiscrMaxSteps``, :487).  ``restore``: model from the checkpoint, the discriminators' weights loaded into ``criterion``, fresh
+    optimizers and schedulers over the LIVE parameters with the checkpointed state loaded into them (the reference takes the pickled
+    optimizer objects, :367-371, whose discriminator parameters are copies nothing else uses).  Returns (model, history) -- per epoch
+    the four means of ``trainAdv_v2`` (:626-629: sums over batches / (batches x frames)), the learning rates, ``evaluate``'s dict and
+    the checkpoint path.  The steps run eagerly (a captured graph of this mode does not exist yet)."""
+    if device is None:
+        device = next(model.parameters()).device
+    start = 1
+    ckpt = None
+    if restore:
+        ckpt, start = load_checkpoint(modeldir, restore_epoch, device)
+        model = ckpt['model']
+        for name, d in criterion.discriminators().items():
+            d.load_state_dict(ckpt[name])
+        log("Restore training from %s and epoch %d" % (modeldir, start))
+    model = model.to(device)
+    criterion.to(device)
+    gen_optimizer, discr_optimizer, gen_scheduler, discr_scheduler = make_adversarial_optimizers(model, criterion, lr, lr_step, lr_gamma)
+    if ckpt is not None:
+        for live, key in ((gen_optimizer, 'gen_optimizer'), (discr_optimizer, 'discr_optimizer'), (gen_scheduler, 'gen_scheduler'),
+                          (discr_scheduler, 'discr_scheduler')):
+            live.load_state_dict(ckpt[key].state_dict())
+    eval_kw = {k: v for k, v in kw.items() if k in ("initial_image", "upscale", "upsample", "disable_temporal")}
+    history = []
+    for epoch in range(start, n_epochs + 1):
+        lr_discr = step_scheduler(discr_optimizer, discr_scheduler)
+        lr_gen = step_scheduler(gen_optimizer, gen_scheduler)
+        steps = disc_initial_steps if (disc_initial_steps is not None and epoch == 1) else disc_steps
+        model.train()
+        criterion.discr_train()
+        totals, frames = [0.0, 0.0, 0.0, 0.0], 0
+        for batch in train_loader:
+            batch = tuple(t.to(device, non_blocking=True) for t in batch)
+            totals = [a + b for a, b in zip(totals, adversarial_step(model, criterion, gen_optimizer, discr_optimizer, batch, steps, **kw))]
+            frames += batch[2].shape[1]
+        means = [t / max(1, frames) for t in totals]
+        log("===> Epoch {} Complete: discr {:.4f}, gen {:.4f}, gt score {:.4f}, pred score {:.4f}".format(epoch, *means))
+        test = evaluate(model, criterion, test_loader, device, **eval_kw) if test_loader is not None else {}
+        path = save_adversarial_checkpoint(modeldir, epoch, model, parameters, criterion, gen_optimizer, discr_optimizer, gen_scheduler,
+                                           discr_scheduler)
+        log("Checkpoint saved to {}".format(path))
+        history.append({'epoch': epoch, 'discr_loss': means[0], 'gen_loss': means[1], 'gt_score': means[2], 'pred_score': means[3],
+                        'lr_gen': lr_gen, 'lr_discr': lr_discr, 'test': test, 'checkpoint': path})
+    return model, history
 
 
 def _optimizer_state_tensors(optimizer):
