@@ -185,6 +185,24 @@ int isrLossUnshadedBackward(const float* gt, const float* pred, const float* pre
                             const float* weights15, unsigned enabled, const float* shading12, float ao_strength, int inverse_ao,
                             const float* gvalues16, float* gpred, float* gprev, void* stream);
 
+/* Inputs of the discriminators of the adversarial terms (SuperresolutionNetwork/losses/lossnet_unshaded.py:313-354, :414-495), one
+ * launch each way.  out [N][C][H][W] = the parts that are present in the order in_a, in_b ([N][5][H][W], the upsampled input and the
+ * warped previous input, or NULL), part8(cur), part8(prev) (cur, prev [N][6][H][W]; prev or NULL): C = 26 (all four), 16 (cur + prev)
+ * or 13 (in_a + cur), any other combination returns -1.  part8(x) = mask, normal / max(|normal|, 1e-7), then colour rgb, ao
+ * (order 0, the generator side) or ao, colour rgb (order 1, train_discriminator).  The colour is the loss shader (shading12,
+ * ao_strength, inverse_ao as isrLossUnshadedForward takes them; no specular, no gate) of the normalised normal, for cur with
+ * cur_raw_normal != 0 of the normal as it arrives.  Every channel of a pixel within `pad` of the border is 0 (the module's pad, shade,
+ * pad again), so the operands are passed unpadded.  isrDiscrInputSupported: W % 4 == 0 and 2 pad < min(H, W); every pointer must be
+ * 16-byte aligned (else -1).
+ * Backward: gout [N][C][H][W] is d L / d out, C names its layout; writes gcur (and gprev unless NULL), [N][6][H][W], 0 at border
+ * pixels.  The inputs get no gradient.  Clamps pass their gradient inclusive at 0 and 1, |x|' = 0 at 0, the normalisation gives
+ * g / 1e-7 where |normal| <= 1e-7 (the conventions of isrLossUnshadedBackward).  No atomics: the same bits on every run. */
+int isrDiscrInputSupported(int N, int H, int W, int pad);
+int isrDiscrInputForward(const float* in_a, const float* in_b, const float* cur, const float* prev, float* out, int N, int H, int W, int pad,
+                         int order, int cur_raw_normal, const float* shading12, float ao_strength, int inverse_ao, void* stream);
+int isrDiscrInputBackward(const float* cur, const float* prev, const float* gout, float* gcur, float* gprev, int C, int N, int H, int W, int pad,
+                          int order, int cur_raw_normal, const float* shading12, float ao_strength, int inverse_ao, void* stream);
+
 /* Recurrent network input of a training clip for frames t > 0 (SuperresolutionNetwork/mainVideoUnshaded.py:436-447,
  * 463-466 with models/videotools.py:8-25,51-87), fused:
  *   previous_output = cat(clamp(p0,-1,1), normalize(p1..3), clamp(p4,0,1), clamp(p5,0,1))   p = prev_raw [B][6][4h][4w]

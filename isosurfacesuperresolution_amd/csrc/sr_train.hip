@@ -6,11 +6,15 @@
 //  * LossNetUnshaded (SuperresolutionNetwork/losses/lossnet_unshaded.py:236-388, l1 / mse / temp-l2 terms on
 //    mask / normal / ao / depth / colour): forward = ONE pass over gt / pred / prev that produces every term's
 //    sum, backward = ONE pass that writes d loss / d pred and d loss / d prev.  The module path
-//    (losses/lossnet_unshaded.py in this package) issues ~150 launches forward and ~200 backward per frame.
+//    (losses/lossnet_unshaded.py in this package) issues ~150 launches forward and ~200 backward per frame;
+//  * the tensors its adversarial terms feed to a discriminator (:313-354, :414-495): normalise, shade, zero the border and
+//    concatenate up to 26 channels in ONE pass, the adjoint w.r.t. the two predictions in one.
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include "../../include/isr_sr_kernels.h"
 #include "sr_finish.h"
+#include "sr_profile.h"
 #include "sr_warp_exact.h"
 
 namespace {
@@ -504,6 +508,199 @@ int fill_loss_params(LossParams& P, const float* gt, const float* pred, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Discriminator inputs of the adversarial terms (lossnet_unshaded.py:313-354 generator side, :414-495 train_discriminator):
+//   out = cat(in_a?, in_b?, part8(cur), part8(prev)?) with a zeroed border of `pad` pixels
+//   part8(x) = mask, normalize(normal), {colour, ao | ao, colour},  colour = the loss shader of (mask, normal', depth, ao),
+//   normal' = the normal as it arrives (cur with cur_raw_normal) or the normalised one
+// The module path is normalise / shade / pad / cat with torch operators, 26 channels per evaluation forward and backward.  The
+// shader and its derivative are eval_fields / backprop_fields of the loss with gate = 1.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int ISR_VARIANT_DISCR_INPUT_FWD = 52;       // ops.VARIANT_NAMES
+constexpr int ISR_VARIANT_DISCR_INPUT_BWD = 53;
+
+struct DiscrInputParams {
+    LossParams L;             // the shader's constants; pred = cur, prev = prev, gpred / gprev = their gradients, N H W pad
+    const float* in_a;        // [N][5][H][W] or NULL
+    const float* in_b;
+    float* out;               // [N][C][H][W]
+    const float* gout;        // backward: d / d out
+    int C, offCur, order, cur_raw;      // offCur: first channel of cur's part in out / gout (the inputs come first)
+};
+
+// one 8-channel part at one pixel: o = mask, normal xyz, then colour rgb + ao (order 0) or ao + colour rgb (order 1)
+struct PartEval { Fields f; float nh[3], len; };
+
+__device__ __forceinline__ void discr_part_eval(const LossParams& P, const float (&x)[6], bool raw, PartEval& e)
+{
+    e.len = sqrtf(x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
+    const float den = fmaxf(e.len, 1e-7f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e.nh[k] = x[1 + k] / den;
+    const float xs[6] = {x[0], raw ? x[1] : e.nh[0], raw ? x[2] : e.nh[1], raw ? x[3] : e.nh[2], x[4], x[5]};
+    eval_fields(P, xs, 1.0f, e.f);
+}
+
+__device__ __forceinline__ void discr_part_forward(const LossParams& P, const float (&x)[6], bool raw, int order, float (&o)[8])
+{
+    PartEval e;
+    discr_part_eval(P, x, raw, e);
+    o[0] = x[0]; o[1] = e.nh[0]; o[2] = e.nh[1]; o[3] = e.nh[2];
+    // (selects, not a computed index: the arrays stay in registers)
+    o[4] = order ? x[5] : e.f.col[0]; o[5] = order ? e.f.col[0] : e.f.col[1];
+    o[6] = order ? e.f.col[1] : e.f.col[2]; o[7] = order ? e.f.col[2] : x[5];
+}
+
+__device__ __forceinline__ void discr_part_backward(const LossParams& P, const float (&x)[6], bool raw, int order, const float (&g)[8], float (&gx)[6])
+{
+    PartEval e;
+    discr_part_eval(P, x, raw, e);
+    // through the shader: mask, ao and the normal it was given (no gate, the depth is not read)
+    const FieldGrad fg = {g[0], {0.f, 0.f, 0.f}, order ? g[4] : g[7], 0.f, {order ? g[5] : g[4], order ? g[6] : g[5], order ? g[7] : g[6]}};
+    float gs[6];
+    backprop_fields(P, e.f, 1.0f, fg, gs);
+    gx[0] = gs[0]; gx[4] = 0.f; gx[5] = gs[5];
+    // through the normalisation: the normal channels' own gradient, and the shader's where it read the normalised normal
+    float dn[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dn[k] = g[1 + k] + (raw ? 0.f : gs[1 + k]);
+    if (e.len > 1e-7f) {
+        const float dot = e.nh[0] * dn[0] + e.nh[1] * dn[1] + e.nh[2] * dn[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gx[1 + k] = (dn[k] - e.nh[k] * dot) / e.len;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gx[1 + k] = dn[k] / 1e-7f;
+    }
+    if (raw) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gx[1 + k] += gs[1 + k];
+    }
+}
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ float& lane_of(float4& v, int k) { return reinterpret_cast<float*>(&v)[k]; }
+
+// one thread = four horizontally adjacent pixels of one image, every channel of them: 16-byte loads and stores, no atomics
+template <bool BACKWARD>
+__global__ __launch_bounds__(256) void discr_input_kernel(const DiscrInputParams D)
+{
+    const LossParams& P = D.L;
+    const int QW = P.W / 4;
+    const long long quadsPerImage = (long long)QW * P.H;
+    const long long quads = quadsPerImage * P.N;
+    const size_t plane = (size_t)P.H * P.W;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int offCur = D.offCur, offPrev = offCur + 8;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long long)gridDim.x * 256) {
+        const int img = (int)(q / quadsPerImage);
+        const long long r = q % quadsPerImage;
+        const int Y = (int)(r / QW), X0 = 4 * (int)(r % QW);
+        const size_t pix = (size_t)Y * P.W + X0;
+        const size_t base6 = (size_t)img * 6 * plane + pix, base5 = (size_t)img * 5 * plane + pix, baseC = (size_t)img * D.C * plane + pix;
+        // a quad with no pixel inside the border frame: zeros, nothing is read
+        const bool any = Y >= P.pad && Y < P.H - P.pad && X0 + 3 >= P.pad && X0 < P.W - P.pad;
+        bool in[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) in[k] = any && X0 + k >= P.pad && X0 + k < P.W - P.pad;
+        if (!BACKWARD) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float* src = s ? D.in_b : D.in_a;
+                if (!src) continue;
+                const int off = s && D.in_a ? 5 : 0;
+#pragma unroll
+                for (int c = 0; c < 5; ++c) {
+                    float4 v = any ? ld4(src + base5 + c * plane) : zero4;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) if (!in[k]) lane_of(v, k) = 0.f;
+                    st4(D.out + baseC + (size_t)(off + c) * plane, v);
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float* src = s ? P.prev : P.pred;
+            if (!src) continue;
+            float* gdst = s ? P.gprev : P.gpred;
+            if (BACKWARD && !gdst) continue;
+            const bool raw = s == 0 && D.cur_raw != 0;
+            const int off = s ? offPrev : offCur;
+            float4 x4[6], o4[8];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) x4[c] = any ? ld4(src + base6 + c * plane) : zero4;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) o4[c] = (BACKWARD && any) ? ld4(D.gout + baseC + (size_t)(off + c) * plane) : zero4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float x[6], o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gx[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int c = 0; c < 6; ++c) x[c] = lane_of(x4[c], k);
+                if (in[k]) {
+                    if (!BACKWARD) {
+                        discr_part_forward(P, x, raw, D.order, o);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) o[c] = lane_of(o4[c], k);
+                        discr_part_backward(P, x, raw, D.order, o, gx);
+                    }
+                }
+                if (!BACKWARD) {
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) lane_of(o4[c], k) = o[c];
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) lane_of(x4[c], k) = gx[c];
+                }
+            }
+            if (!BACKWARD) {
+#pragma unroll
+                for (int c = 0; c < 8; ++c) st4(D.out + baseC + (size_t)(off + c) * plane, o4[c]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) st4(gdst + base6 + c * plane, x4[c]);
+            }
+        }
+    }
+}
+
+bool discr_input_shape_ok(int N, int H, int W, int pad)
+{
+    return N > 0 && H > 0 && W > 0 && !(W & 3) && pad >= 0 && 2 * pad < H && 2 * pad < W;
+}
+
+bool aligned16(const void* p) { return !(((uintptr_t)p) & 15); }
+
+// C of the parts that are present, or 0 for a combination no adversarial term has
+int discr_input_channels(bool a, bool b, bool prev)
+{
+    if (a && b && prev) return 26;
+    if (!a && !b && prev) return 16;
+    if (a && !b && !prev) return 13;
+    return 0;
+}
+
+int fill_discr_params(DiscrInputParams& D, const float* in_a, const float* in_b, const float* cur, const float* prev, int N, int H, int W, int pad,
+                      int order, int cur_raw_normal, const float* shading12, float ao_strength, int inverse_ao)
+{
+    if (!cur || !shading12 || !discr_input_shape_ok(N, H, W, pad) || (order != 0 && order != 1)) return -1;
+    if (!aligned16(in_a) || !aligned16(in_b) || !aligned16(cur) || !aligned16(prev)) return -1;
+    D = {};
+    D.C = discr_input_channels(in_a != nullptr, in_b != nullptr, prev != nullptr);       // (the backward sets its own)
+    LossParams& P = D.L;
+    P.pred = cur; P.prev = prev; P.N = N; P.H = H; P.W = W; P.pad = pad;
+    for (int k = 0; k < 3; ++k) {
+        P.ambmat[k] = shading12[k]; P.diffmat[k] = shading12[3 + k]; P.light[k] = shading12[6 + k]; P.bg[k] = shading12[9 + k];
+    }
+    P.ao_strength = ao_strength; P.inverse_ao = inverse_ao;
+    D.in_a = in_a; D.in_b = in_b; D.order = order; D.cur_raw = cur_raw_normal ? 1 : 0;
+    D.offCur = (in_a ? 5 : 0) + (in_b ? 5 : 0);
+    const long long blocks = ((long long)N * H * (W / 4) + 255) / 256;
+    P.blocks = (int)(blocks > 2048 ? 2048 : blocks);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Recurrent network input of a training clip (mainVideoUnshaded.py:436-447,463-466), frames t > 0:
 //   previous_output = cat(clamp(p0,-1,1), normalize(p1..3), clamp(p4,0,1), clamp(p5,0,1))     p = raw prediction t-1
 //   warped          = VideoTools.warp_upscale(previous_output, flow[t-1], 4, special_mask=True)
@@ -897,6 +1094,32 @@ int isrLossUnshadedBackward(const float* gt, const float* pred, const float* pre
     P.gout = gvalues16; P.gpred = gpred; P.gprev = gprev;
     hipLaunchKernelGGL(loss_unshaded_kernel<true>, dim3(P.blocks), dim3(256), 0, (hipStream_t)stream, P);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrDiscrInputSupported(int N, int H, int W, int pad) { return discr_input_shape_ok(N, H, W, pad) ? 1 : 0; }
+
+int isrDiscrInputForward(const float* in_a, const float* in_b, const float* cur, const float* prev, float* out, int N, int H, int W, int pad,
+                         int order, int cur_raw_normal, const float* shading12, float ao_strength, int inverse_ao, void* stream)
+{
+    DiscrInputParams D;
+    if (!out || !aligned16(out)) return -1;
+    if (int rc = fill_discr_params(D, in_a, in_b, cur, prev, N, H, W, pad, order, cur_raw_normal, shading12, ao_strength, inverse_ao)) return rc;
+    if (!D.C) return -1;
+    D.out = out;
+    return isr_launch(ISR_VARIANT_DISCR_INPUT_FWD, 0.0, discr_input_kernel<false>, dim3(D.L.blocks), dim3(256), 0, (hipStream_t)stream, D);
+}
+
+int isrDiscrInputBackward(const float* cur, const float* prev, const float* gout, float* gcur, float* gprev, int C, int N, int H, int W, int pad,
+                          int order, int cur_raw_normal, const float* shading12, float ao_strength, int inverse_ao, void* stream)
+{
+    DiscrInputParams D;
+    if (!gout || !gcur || !aligned16(gout) || !aligned16(gcur) || !aligned16(gprev) || (gprev && !prev)) return -1;
+    if (int rc = fill_discr_params(D, nullptr, nullptr, cur, prev, N, H, W, pad, order, cur_raw_normal, shading12, ao_strength, inverse_ao)) return rc;
+    // C names the layout of gout: the 8-channel parts follow the inputs that the forward copied
+    if (C != (prev ? 26 : 13) && !(prev && C == 16)) return -1;
+    D.C = C; D.offCur = C == 26 ? 10 : (C == 13 ? 5 : 0);
+    D.gout = gout; D.L.gpred = gcur; D.L.gprev = gprev;
+    return isr_launch(ISR_VARIANT_DISCR_INPUT_BWD, 0.0, discr_input_kernel<true>, dim3(D.L.blocks), dim3(256), 0, (hipStream_t)stream, D);
 }
 
 int isrRecurrentInputForward(const float* prev_raw, const float* input, const float* flow, float* net_input, float* warped,

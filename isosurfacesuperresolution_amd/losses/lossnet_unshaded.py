@@ -18,7 +18,8 @@ static ``pad``) for the l1 / mse(l2) / temp-l2 terms of the README recipe
   ``all`` (``:80-105``, ``:313-354``): each owns a discriminator built by ``LossBuilder.gan_loss(opt.discriminator, ...)`` and adds
   ``weight * BCE-with-logits(discriminator(input), 1)`` to the generator's loss; ``train_discriminator`` (``:414-495``) is the
   discriminators' own loss on a ground-truth and a predicted input.  The tensors fed to a discriminator (normalise, shade, pad,
-  concatenate) are assembled with torch operators; the networks run on ``ops.conv3x3`` / ``ops.conv3x3_s2``.
+  concatenate) are ``ops.discriminator_input``: one launch each way on the GPU where ``fused`` and its predicate hold, the composition
+  of torch operators otherwise; the networks run on ``ops.conv3x3`` / ``ops.conv3x3_s2``.
 
 Parity: the l1 / mse / temp-l2 terms are checked against hand-derived values; the adversarial terms, ``train_discriminator`` and the
 discriminators against values recorded from the reference's own modules (tests/golden/make_gan_fixtures.py, which supplies an empty
@@ -127,7 +128,8 @@ class LossNetUnshaded(nn.Module):
         self.lazy_values = False
         # GPU tensors: the whole forward is ONE launch of isrLossUnshadedForward (+ a one-workgroup reduction) and the
         # whole backward ONE launch of isrLossUnshadedBackward (csrc/sr_train.hip) instead of ~350 PyTorch launches per
-        # frame; fused = False keeps the module path below (what the CPU runs, and what the GPU tests compare against)
+        # frame, and each adversarial term's discriminator input is one launch each way (ops.discriminator_input);
+        # fused = False keeps the module path below (what the CPU runs, and what the GPU tests compare against)
         self.fused = True
         self._fused_cfg = (None, None)
         self.padding = padding
@@ -212,19 +214,27 @@ class LossNetUnshaded(nn.Module):
     @staticmethod
     def pad(img, border):
         """Overwrites a ``border``-pixel frame of ``img`` with zeros (size unchanged)."""
-        if border == 0:
-            return img
-        b, c, h, w = img.shape
-        inner = img[:, :, border:h - border, border:w - border]
-        out = F.pad(inner, (border, border, border, border), 'constant', 0)
-        assert out.shape[2] == h and out.shape[3] == w
-        return out
+        return ops.pad_border(img, border)
 
     def _fusable(self, gt, pred, prev):
         return (self.fused and pred.is_cuda and gt.is_cuda and pred.dtype == torch.float32 and gt.dtype == torch.float32
                 and pred.shape[3] % 4 == 0 and 2 * self.padding < min(pred.shape[2], pred.shape[3])
                 and not self.shading.enable_specular
                 and (prev is None or (prev.is_cuda and prev.dtype == torch.float32 and prev.shape == pred.shape)))
+
+    def _fused_inputs(self, cur, prev, input, prev_input):
+        """Whether the discriminators' inputs of these four tensors are assembled by ``ops.discriminator_input``'s kernels (one launch
+        per term and direction) instead of operator by operator."""
+        return (self.fused and ops.DISCR_INPUT_FUSED and None not in (cur, prev, input, prev_input)
+                and ops.discriminator_input_supported(cur, prev, input, prev_input, padding=self.padding, shading=self.shading))
+
+    # (key, attribute prefix, value key, parts of (input, prev_input, cur, prev) that the term's discriminator reads)
+    _ADVERSARIAL_TERMS = (('adv', '', 'discr_pred', (True, True, True, True)), ('tgan', 'temp_', 'temp_discr_pred', (False, False, True, True)),
+                          ('sgan', 'spatial_', 'spatial_discr_pred', (True, False, True, False)))
+
+    def _fused_term_input(self, parts, input, prev_input, cur, prev, order, cur_raw_normal):
+        return ops.discriminator_input(cur, prev if parts[3] else None, input if parts[0] else None, prev_input if parts[1] else None,
+                                       padding=self.padding, shading=self.shading, order=order, cur_raw_normal=cur_raw_normal)
 
     def _forward_fused(self, gt, pred, prev):
         fused_weights = {k: v for k, v in self.weight_dict.items() if k[0] in ops.LOSS_KINDS}       # (the adversarial terms are added by forward)
@@ -250,9 +260,13 @@ class LossNetUnshaded(nn.Module):
             # the fused launch computes the l1 / mse / temp-l2 part; the adversarial terms are added to its total
             total, values = self._forward_fused(gt, pred, prev_pred_warped)
             if self.has_discriminator:
-                pred_pad = LossNetUnshaded.pad(pred, self.padding)
-                adv, adv_values = self._adversarial_terms(pred_pad, self.shading(pred_pad), input, prev_input_warped,
-                                                          LossNetUnshaded.pad(prev_pred_warped, self.padding))
+                if self._fused_inputs(pred, prev_pred_warped, input, prev_input_warped):
+                    # the assembly kernel zeroes the border itself and shades: the unpadded prediction goes in
+                    adv, adv_values = self._adversarial_terms(pred, None, input, prev_input_warped, prev_pred_warped)
+                else:
+                    pred_pad = LossNetUnshaded.pad(pred, self.padding)
+                    adv, adv_values = self._adversarial_terms(pred_pad, self.shading(pred_pad), input, prev_input_warped,
+                                                              LossNetUnshaded.pad(prev_pred_warped, self.padding))
                 total = total + adv
                 values.update(adv_values)
             return total, values
@@ -313,24 +327,29 @@ class LossNetUnshaded(nn.Module):
         """The generator's adversarial terms (``:313-354``) -> (weighted sum, {'discr_pred' | 'temp_discr_pred' | 'spatial_discr_pred': value}).
         ``pred`` and ``prev_pred_warped`` arrive with their border already zeroed and ``pred_color`` is the shading of that ``pred``: the
         reference pads, then normalises and shades, then pads AGAIN (``:205-208``, ``:333-336``) -- a zeroed normal shades to the ambient
-        term, which the second padding removes."""
+        term, which the second padding removes.  ``pred_color`` None: the fused branch of ``forward``, ``pred`` and
+        ``prev_pred_warped`` arrive UNPADDED and each term's input is one launch of ``ops.discriminator_input``."""
         if input is None or prev_input_warped is None or prev_pred_warped is None:
             raise ValueError("the adversarial terms need the upsampled input, the warped previous input and the warped previous prediction")
-        norm = ScreenSpaceShading.normalize
+        if pred_color is None:
+            total, values = 0.0, {}
+            for key, attr, value_key, parts in self._ADVERSARIAL_TERMS:
+                if (key, 'all') in self.weight_dict:
+                    # generator side: mask, normal, COLOUR, ao, the prediction shaded from its unnormalised normal (:315-319, :322-331)
+                    x = self._fused_term_input(parts, input, prev_input_warped, pred, prev_pred_warped, order=0, cur_raw_normal=True)
+                    loss = getattr(self, attr + 'adv_loss')(getattr(self, attr + 'discriminator')(x))
+                    values[value_key] = loss.detach() if self.lazy_values else loss.item()
+                    total = total + self.weight_dict[(key, 'all')] * loss
+            return total, values
         # generator side: mask, normal, COLOUR, ao (:315-319, :322-331) -- train_discriminator below orders ao before colour
-        pred_with_color = torch.cat([pred[:, 0:1], norm(pred[:, 1:4], dim=1), pred_color, pred[:, 5:6]], dim=1)
-        prev_normal = norm(prev_pred_warped[:, 1:4], dim=1)
-        prev_color = self.shading(torch.cat([prev_pred_warped[:, 0:1], prev_normal, prev_pred_warped[:, 4:6]], dim=1))
-        prev_with_color = torch.cat([prev_pred_warped[:, 0:1], prev_normal, prev_color, prev_pred_warped[:, 5:6]], dim=1)
-        pad = LossNetUnshaded.pad
-        input_pad, prev_input_pad = pad(input, self.padding), pad(prev_input_warped, self.padding)
-        pred_pad, prev_pad = pad(pred_with_color, self.padding), pad(prev_with_color, self.padding)
+        part = dict(padding=self.padding, shading=self.shading, order=0)
+        tensors = (LossNetUnshaded.pad(input, self.padding), LossNetUnshaded.pad(prev_input_warped, self.padding),
+                   ops.discriminator_part(pred, raw_normal=True, color=pred_color, **part), ops.discriminator_part(prev_pred_warped, **part))
         total, values = 0.0, {}
-        for key, value_key, attr, parts in (('adv', 'discr_pred', '', (input_pad, prev_input_pad, pred_pad, prev_pad)),
-                                            ('tgan', 'temp_discr_pred', 'temp_', (pred_pad, prev_pad)),
-                                            ('sgan', 'spatial_discr_pred', 'spatial_', (input_pad, pred_pad))):
+        for key, attr, value_key, parts in self._ADVERSARIAL_TERMS:
             if (key, 'all') in self.weight_dict:
-                loss = getattr(self, attr + 'adv_loss')(getattr(self, attr + 'discriminator')(torch.cat(parts, dim=1)))
+                x = torch.cat([t for t, used in zip(tensors, parts) if used], dim=1)
+                loss = getattr(self, attr + 'adv_loss')(getattr(self, attr + 'discriminator')(x))
                 values[value_key] = loss.detach() if self.lazy_values else loss.item()
                 total = total + self.weight_dict[(key, 'all')] * loss
         return total, values
@@ -340,28 +359,28 @@ class LossNetUnshaded(nn.Module):
         [B, 5, H, W] (mask, normal, depth), the other four [B, 6, H, W] -> (loss, gt score, pred score), each the weighted sum over the
         adversarial terms of ``AdversarialLoss.train_discr`` on a ground-truth and a predicted input."""
         assert self.has_discriminator
-        norm = ScreenSpaceShading.normalize
+        # discriminator side: mask, normal, AO, colour, shaded from the normalised normal (:436) -- the generator side above orders colour
+        # before ao
+        if (self._fused_inputs(gt_high, gt_prev_warped, input, previous_input)
+                and self._fused_inputs(pred_high, pred_prev_warped, input, previous_input)):
+            def term_inputs(parts):
+                return tuple(self._fused_term_input(parts, input, previous_input, cur, prev, order=1, cur_raw_normal=False)
+                             for cur, prev in ((gt_high, gt_prev_warped), (pred_high, pred_prev_warped)))
+        else:
+            part = dict(padding=self.padding, shading=self.shading, order=1)
+            shared = (LossNetUnshaded.pad(input, self.padding), LossNetUnshaded.pad(previous_input, self.padding))
+            sides = tuple(shared + (ops.discriminator_part(cur, **part), ops.discriminator_part(prev, **part))
+                          for cur, prev in ((gt_high, gt_prev_warped), (pred_high, pred_prev_warped)))
 
-        def colorize_and_pad(t):
-            assert t.shape[1] == 6
-            mask, normal, ao = t[:, 0:1], norm(t[:, 1:4], dim=1), t[:, 5:6]
-            color = self.shading(torch.cat([mask, normal, t[:, 4:6]], dim=1))
-            # discriminator side: mask, normal, AO, colour (:436) -- the generator side above orders colour before ao
-            return LossNetUnshaded.pad(torch.cat([mask, normal, ao, color], dim=1), self.padding)
-
-        input = LossNetUnshaded.pad(input, self.padding)
-        previous_input = LossNetUnshaded.pad(previous_input, self.padding)
-        gt_high, pred_high = colorize_and_pad(gt_high), colorize_and_pad(pred_high)
-        gt_prev_warped, pred_prev_warped = colorize_and_pad(gt_prev_warped), colorize_and_pad(pred_prev_warped)
+            def term_inputs(parts):
+                return tuple(torch.cat([t for t, used in zip(side, parts) if used], dim=1) for side in sides)
         discr_loss = gt_score = pred_score = 0
-        for key, attr, gt_parts, pred_parts in (
-                ('adv', '', (input, previous_input, gt_high, gt_prev_warped), (input, previous_input, pred_high, pred_prev_warped)),
-                ('tgan', 'temp_', (gt_high, gt_prev_warped), (pred_high, pred_prev_warped)),
-                ('sgan', 'spatial_', (input, gt_high), (input, pred_high))):
+        for key, attr, _, parts in self._ADVERSARIAL_TERMS:
             if (key, 'all') in self.weight_dict:
                 adv = getattr(self, attr + 'adv_loss')
                 adv.lazy_values = self.lazy_values
-                loss0, gt0, pred0 = adv.train_discr(torch.cat(gt_parts, dim=1), torch.cat(pred_parts, dim=1), getattr(self, attr + 'discriminator'))
+                gt_input, pred_input = term_inputs(parts)
+                loss0, gt0, pred0 = adv.train_discr(gt_input, pred_input, getattr(self, attr + 'discriminator'))
                 w = self.weight_dict[(key, 'all')]
                 discr_loss, gt_score, pred_score = discr_loss + w * loss0, gt_score + w * gt0, pred_score + w * pred0
         return discr_loss, gt_score, pred_score

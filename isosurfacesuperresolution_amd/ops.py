@@ -114,6 +114,11 @@ def _bind(lib):
     lib.isrLossUnshadedForward.restype = ci
     lib.isrLossUnshadedBackward.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, ctypes.c_uint, vp, cf, ci, vp, vp, vp, vp]
     lib.isrLossUnshadedBackward.restype = ci
+    lib.isrDiscrInputSupported.argtypes = [ci, ci, ci, ci]; lib.isrDiscrInputSupported.restype = ci
+    lib.isrDiscrInputForward.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, cf, ci, vp]
+    lib.isrDiscrInputForward.restype = ci
+    lib.isrDiscrInputBackward.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, cf, ci, vp]
+    lib.isrDiscrInputBackward.restype = ci
     lib.isrRecurrentInputForward.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ll, ll, vp]; lib.isrRecurrentInputForward.restype = ci
     lib.isrRecurrentInputBackward.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ll, vp]; lib.isrRecurrentInputBackward.restype = ci
     lib.isrConvF16WeightBytes.argtypes = [ci, ci]; lib.isrConvF16WeightBytes.restype = ll
@@ -416,7 +421,9 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  42: "gate_grad_sum_kernel", 43: "gate_backward_kernel", 44: "gate_param_grad_kernel",
                  45: "shuffle_tail_dgrad_kernel", 46: "shuffle_tail_wgrad_kernel", 47: "shuffle_tail_wgrad_sum_kernel",
                  # the stride-2 convolution of the discriminators (csrc/sr_conv_stride2.hip)
-                 48: "conv3x3s2_fwd_kernel", 49: "conv3x3s2_dgrad_kernel", 50: "conv3x3s2_wgrad_kernel", 51: "conv3x3s2_wgrad_sum_kernel"}
+                 48: "conv3x3s2_fwd_kernel", 49: "conv3x3s2_dgrad_kernel", 50: "conv3x3s2_wgrad_kernel", 51: "conv3x3s2_wgrad_sum_kernel",
+                 # the discriminator inputs of the adversarial terms (csrc/sr_train.hip)
+                 52: "discr_input_fwd_kernel", 53: "discr_input_bwd_kernel"}
 
 
 def debug_switches():
@@ -2078,6 +2085,131 @@ def loss_unshaded_config(weight_dict, padding, shading):
 def loss_unshaded(gt, pred, prev, cfg):
     """-> values[16] (differentiable w.r.t. pred and prev through values[15], the weighted total)."""
     return _LossUnshadedFunction.apply(gt, pred, prev, cfg)
+
+
+# ---- discriminator inputs of the adversarial terms (csrc/sr_train.hip: discr_input_kernel) -------------------------------------
+# ISR_DISCR_INPUT_FUSED=0: the torch composition everywhere (A/B runs of tools/bench_gan_train.py)
+DISCR_INPUT_FUSED = os.environ.get("ISR_DISCR_INPUT_FUSED", "1") != "0"
+_DISCR_CHANNELS = {(True, True, True): 26, (False, False, True): 16, (True, False, False): 13}     # (input, prev_input, prev) present
+
+
+def pad_border(img, border):
+    """Overwrites a ``border``-pixel frame of ``img`` with zeros (size unchanged): ``LossNetUnshaded.pad``."""
+    if border == 0:
+        return img
+    b, c, h, w = img.shape
+    inner = img[:, :, border:h - border, border:w - border]
+    out = F.pad(inner, (border, border, border, border), 'constant', 0)
+    assert out.shape[2] == h and out.shape[3] == w
+    return out
+
+
+def discriminator_part(t, *, padding, shading, order, raw_normal=False, color=None):
+    """One 8-channel part of a discriminator input with torch operators, ``t`` [B, 6, H, W]: mask, normalised normal, then colour and
+    ao (``order`` 0, the generator side) or ao and colour (``order`` 1, ``train_discriminator``), border zeroed.  The colour is
+    ``shading`` of the normalised normal, with ``raw_normal`` of ``t`` as it is; ``color``: that shading where the caller has it."""
+    from .utils import ScreenSpaceShading
+    assert t.shape[1] == 6
+    mask, normal, ao = t[:, 0:1], ScreenSpaceShading.normalize(t[:, 1:4], dim=1), t[:, 5:6]
+    if color is None:
+        color = shading(t if raw_normal else torch.cat([mask, normal, t[:, 4:6]], dim=1))
+    return pad_border(torch.cat([mask, normal, color, ao] if order == 0 else [mask, normal, ao, color], dim=1), padding)
+
+
+def _discriminator_input_torch(cur, prev, input, prev_input, padding, shading, order, cur_raw_normal):
+    parts = [pad_border(t, padding) for t in (input, prev_input) if t is not None]
+    parts.append(discriminator_part(cur, padding=padding, shading=shading, order=order, raw_normal=cur_raw_normal))
+    if prev is not None:
+        parts.append(discriminator_part(prev, padding=padding, shading=shading, order=order))
+    return torch.cat(parts, dim=1)
+
+
+def _discr_operand(t, channels, like):
+    return t is None or (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.device == like.device
+                         and t.shape == (like.shape[0], channels, like.shape[2], like.shape[3])
+                         and (not t.is_contiguous() or t.data_ptr() % 16 == 0))
+
+
+def discriminator_input_supported(cur, prev=None, input=None, prev_input=None, *, padding, shading=None):
+    """Whether ``discriminator_input`` takes the kernel route for these operands: fp32 GPU tensors of one size, one of the three part
+    combinations, a width that is a multiple of 4, ``2 * padding < min(H, W)``, 16-byte aligned storage, no specular term."""
+    if not (torch.is_tensor(cur) and cur.is_cuda and cur.dim() == 4 and cur.shape[1] == 6 and _discr_operand(cur, 6, cur)):
+        return False
+    if (input is not None, prev_input is not None, prev is not None) not in _DISCR_CHANNELS:
+        return False
+    if not (_discr_operand(prev, 6, cur) and _discr_operand(input, 5, cur) and _discr_operand(prev_input, 5, cur)):
+        return False
+    if shading is not None and shading.enable_specular:
+        return False
+    n, _, h, w = cur.shape
+    return bool(_sr().isrDiscrInputSupported(n, h, w, int(padding)))
+
+
+_discr_shading_cache = {}
+
+
+def _discr_shading(shading):
+    """(shading12, ao strength, inverse_ao) as the kernels take them (the layout of ``loss_unshaded_config``)."""
+    v = shading.packed_parameters()
+    key = (tuple(v), float(shading._ao), bool(shading.inverse_ao))
+    hit = _discr_shading_cache.get(key)
+    if hit is None:
+        amb, diff, light, mat, bg = v[0:3], v[3:6], v[9:12], v[12:15], v[15:18]
+        sh = [a * m for a, m in zip(amb, mat)] + [d * m for d, m in zip(diff, mat)] + list(light) + list(bg)
+        if len(_discr_shading_cache) > 64:
+            _discr_shading_cache.clear()
+        hit = _discr_shading_cache[key] = ((ctypes.c_float * 12)(*sh), key[1], int(key[2]))
+    return hit
+
+
+class _DiscrInputFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cur, prev, input, prev_input, cfg):
+        cur, prev, input, prev_input = (t.contiguous() if t is not None else None for t in (cur, prev, input, prev_input))
+        n, _, h, w = cur.shape
+        pad, order, raw, (sh, ao, inv) = cfg
+        channels = _DISCR_CHANNELS[(input is not None, prev_input is not None, prev is not None)]
+        out = torch.empty((n, channels, h, w), dtype=torch.float32, device=cur.device)
+        rc = _sr().isrDiscrInputForward(_ptr(input), _ptr(prev_input), _ptr(cur), _ptr(prev), _ptr(out), n, h, w, pad, order, raw, sh, ao, inv,
+                                        _stream())
+        if rc != 0:
+            raise RuntimeError("isrDiscrInputForward failed (%d)" % rc)
+        ctx.cfg, ctx.channels = cfg, channels
+        ctx.save_for_backward(cur, prev)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        cur, prev = ctx.saved_tensors
+        pad, order, raw, (sh, ao, inv) = ctx.cfg
+        n, _, h, w = cur.shape
+        gout = gout.contiguous()
+        gcur = torch.empty_like(cur)
+        gprev = torch.empty_like(prev) if prev is not None and ctx.needs_input_grad[1] else None
+        rc = _sr().isrDiscrInputBackward(_ptr(cur), _ptr(prev), _ptr(gout), _ptr(gcur), _ptr(gprev), ctx.channels, n, h, w, pad, order, raw,
+                                         sh, ao, inv, _stream())
+        if rc != 0:
+            raise RuntimeError("isrDiscrInputBackward failed (%d)" % rc)
+        return gcur, gprev, None, None, None
+
+
+def discriminator_input(cur, prev=None, input=None, prev_input=None, *, padding, shading, order, cur_raw_normal):
+    """The tensor a discriminator of the adversarial terms reads, [B, 26 | 16 | 13, H, W]: the parts that are given in the order
+    ``input``, ``prev_input`` ([B, 5, H, W]: the upsampled input, the warped previous input), then ``discriminator_part`` of ``cur`` and
+    of ``prev`` ([B, 6, H, W]), a ``padding``-pixel border zeroed; differentiable w.r.t. ``cur`` and ``prev``.  The operands are passed
+    unpadded.  On the GPU one launch forward and one backward (``isrDiscrInputForward`` / ``Backward``) instead of normalise, shade,
+    pad and concatenate with torch operators; CPU tensors, shapes the predicate refuses, a shader with its specular term on and
+    ``DISCR_INPUT_FUSED = False`` take that composition."""
+    if order not in (0, 1):
+        raise ValueError("order is 0 (mask, normal, colour, ao) or 1 (mask, normal, ao, colour)")
+    if cur.shape[1] != 6:
+        raise ValueError("cur is [B, 6, H, W] (mask, normal, depth, ao)")
+    if (input is not None, prev_input is not None, prev is not None) not in _DISCR_CHANNELS:
+        raise ValueError("a discriminator reads input + prev_input + cur + prev (26 channels), cur + prev (16) or input + cur (13)")
+    if DISCR_INPUT_FUSED and discriminator_input_supported(cur, prev, input, prev_input, padding=padding, shading=shading):
+        cfg = (int(padding), int(order), int(bool(cur_raw_normal)), _discr_shading(shading))
+        return _DiscrInputFunction.apply(cur, prev, input, prev_input, cfg)
+    return _discriminator_input_torch(cur, prev, input, prev_input, padding, shading, order, bool(cur_raw_normal))
 
 
 @contextlib.contextmanager

@@ -311,14 +311,15 @@ def train_step(model, criterion, optimizer, batch, clip_loss=None, **kw):
     return float(loss_sum.item()) / target.shape[1]
 
 
-def make_adversarial_optimizers(model, criterion, lr=1e-4, lr_step=500, lr_gamma=0.5):
+def make_adversarial_optimizers(model, criterion, lr=1e-4, lr_step=500, lr_gamma=0.5, capturable=False):
     """The two optimizers of mainVideoUnshaded.py:303-312: Adam(lr) on the generator, Adam(lr * 0.5) on the discriminators' trainable
-    parameters, StepLR(lr_step, lr_gamma) on both -> (gen_optimizer, discr_optimizer, gen_scheduler, discr_scheduler)."""
+    parameters, StepLR(lr_step, lr_gamma) on both -> (gen_optimizer, discr_optimizer, gen_scheduler, discr_scheduler).
+    ``capturable``: both Adams keep their step counts on the device, as ``GraphedAdversarialStep`` needs them."""
     discr_params = [p for p in criterion.get_discr_parameters() if p.requires_grad]
     if not discr_params:
         raise ValueError("make_adversarial_optimizers: the criterion has no discriminator (no adv / gan / tgan / sgan term in its losses)")
-    gen_optimizer = torch.optim.Adam(list(model.parameters()), lr=lr)
-    discr_optimizer = torch.optim.Adam(discr_params, lr=lr * 0.5)
+    gen_optimizer = torch.optim.Adam(list(model.parameters()), lr=lr, capturable=capturable)
+    discr_optimizer = torch.optim.Adam(discr_params, lr=lr * 0.5, capturable=capturable)
     return (gen_optimizer, discr_optimizer, torch.optim.lr_scheduler.StepLR(gen_optimizer, lr_step, lr_gamma),
             torch.optim.lr_scheduler.StepLR(discr_optimizer, lr_step, lr_gamma))
 
@@ -373,6 +374,12 @@ def adversarial_step(model, criterion, gen_optimizer, discr_optimizer, batch, di
     parameters are switched to ``requires_grad_(False)`` and back: the reference computes their gradients and zeroes them unused
     (:508-509, :573-574), so every parameter ends the same.  Both phases go through ``backward`` (deferred weight gradients);
     ``kw`` goes to the two clip loops (initial_image, upscale, upsample, disable_temporal)."""
+    return tuple(float(v) for v in _adversarial_step_tensors(model, criterion, gen_optimizer, discr_optimizer, batch, disc_steps, **kw))   # (the step's read-back)
+
+
+def _adversarial_step_tensors(model, criterion, gen_optimizer, discr_optimizer, batch, disc_steps, **kw):
+    """``adversarial_step`` without its read-back: the four results as they come off the device (tensors), so that the same body can be
+    enqueued eagerly or captured (``GraphedAdversarialStep``)."""
     input, flow, target = batch
     dkw = {k: v for k, v in kw.items() if k != "fused_recurrence"}
     discr_loss = gen_loss = None
@@ -398,7 +405,7 @@ def adversarial_step(model, criterion, gen_optimizer, discr_optimizer, batch, di
     finally:
         for p in discr_params:
             p.requires_grad_(True)
-    return tuple(float(v) for v in (discr_loss, gen_loss, gt_score, pred_score))       # (the step's read-back)
+    return discr_loss, gen_loss, gt_score, pred_score
 
 
 DISCRIMINATOR_KEYS = ('discriminator', 'temp_discriminator', 'spatial_discriminator')
@@ -431,7 +438,8 @@ def fit_adversarial(model, criterion, train_loader, test_loader, modeldir, n_epo
     optimizers and schedulers over the LIVE parameters with the checkpointed state loaded into them (the reference takes the pickled
     optimizer objects, :367-371, whose discriminator parameters are copies nothing else uses).  Returns (model, history) -- per epoch
     the four means of ``trainAdv_v2`` (:626-629: sums over batches / (batches x frames)), the learning rates, ``evaluate``'s dict and
-    the checkpoint path.  The steps run eagerly (a captured graph of this mode does not exist yet)."""
+    the checkpoint path.  The steps run eagerly (``GraphedAdversarialStep`` is the captured form of one step, for a loop with fixed batch
+    shapes)."""
     if device is None:
         device = next(model.parameters()).device
     start = 1
@@ -565,6 +573,70 @@ class GraphedTrainStep:
         self.graph.replay()
         ops.invalidate_weight_images()
         return self.loss
+
+
+class GraphedAdversarialStep:
+    """``adversarial_step`` (``disc_steps`` discriminator steps, then ``disc_steps`` generator steps with the discriminators switched to
+    ``requires_grad_(False)``) captured ONCE in one HIP graph on one stream and replayed, in the manner of ``GraphedTrainStep``: static
+    batch buffers, ``warmup`` real steps on the example batch that are undone in place -- the model, every discriminator and both
+    optimizers are back where they were before the first replay -- and ``ops.invalidate_weight_images()`` after every replay.
+
+    ``__call__(batch)`` -> (discr_loss, gen_loss, gt_score, pred_score) as device tensors that the next replay overwrites; nothing is
+    read back.  The optimizers must be ones a capture can record: Adam built with ``capturable=True``
+    (``make_adversarial_optimizers(..., capturable=True)``), or an optimizer without a host-side step count such as ``torch.optim.SGD``.
+    A learning rate held as a Python float is part of the captured graph: a scheduler needs ``lr`` as a tensor.  ``kw`` goes to the two
+    clip loops as in ``adversarial_step``."""
+
+    def __init__(self, model, criterion, gen_optimizer, discr_optimizer, example_batch, disc_steps=2, warmup=2, **kw):
+        if disc_steps < 1:
+            raise ValueError("GraphedAdversarialStep: disc_steps must be at least 1")
+        for name, opt in (("gen_optimizer", gen_optimizer), ("discr_optimizer", discr_optimizer)):
+            if not all(g.get("capturable", True) for g in opt.param_groups):
+                raise ValueError("GraphedAdversarialStep: %s was built with capturable=False "
+                                 "(make_adversarial_optimizers(..., capturable=True))" % name)
+        self.model, self.criterion, self.gen_optimizer, self.discr_optimizer = model, criterion, gen_optimizer, discr_optimizer
+        self.disc_steps, self.kw = disc_steps, kw
+        self.static = tuple(torch.empty_like(t) for t in example_batch)
+        for dst, src in zip(self.static, example_batch):
+            dst.copy_(src)
+        # (the criterion's state_dict is its discriminators': the loss modules and the shader hold no parameters or buffers)
+        before = ((_snapshot_training_state(model, gen_optimizer), _snapshot_training_state(criterion, discr_optimizer))
+                  if warmup > 0 else None)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._eager()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        self._zero_grad()
+        # The step's FIRST use of the discriminators' weights follows a generator phase that left them alone: their kernel-layout images
+        # would be taken from the cache and no refresh would be recorded, so that the first replay -- on the weights put back below --
+        # would read the warm-up's.  With every image declared stale the capture records a refresh at each weight's first use.
+        ops.invalidate_weight_images()
+        with ops.graph_capture(self.graph):
+            self.results = self._eager()
+        if before is not None:
+            _restore_training_state(model, gen_optimizer, before[0])
+            _restore_training_state(criterion, discr_optimizer, before[1])
+        self._zero_grad()
+        ops.invalidate_weight_images()
+
+    def _zero_grad(self):
+        self.gen_optimizer.zero_grad(set_to_none=True)
+        self.discr_optimizer.zero_grad(set_to_none=True)
+
+    def _eager(self):
+        return _adversarial_step_tensors(self.model, self.criterion, self.gen_optimizer, self.discr_optimizer, self.static, self.disc_steps,
+                                         **self.kw)
+
+    def __call__(self, batch):
+        for dst, src in zip(self.static, batch):
+            dst.copy_(src, non_blocking=True)
+        self.graph.replay()
+        ops.invalidate_weight_images()
+        return self.results
 
 
 class DataParallelTrainer:
