@@ -176,7 +176,7 @@ int isrReconResidualBackward(const float* gy, float* gx, int N, int Cout, int Ci
  * is off in the loss shader, lossnet_unshaded.py:116-126).  values16 (device): the 15 term means (0 for terms that
  * are not enabled) and [15] = sum of weight * mean.  workspace: isrLossUnshadedWorkspace() bytes.
  * Backward: gvalues16 (device) is d L / d values16, of which only [15] is read; writes gpred (and gprev unless
- * NULL), both [N][6][H][W]. */
+ * NULL), both [N][6][H][W].  gt, pred, prev, gpred and gprev must be 16-byte aligned (else -1, nothing is launched). */
 long long isrLossUnshadedWorkspace(void);
 int isrLossUnshadedForward(const float* gt, const float* pred, const float* prev, int N, int H, int W, int pad,
                            const float* weights15, unsigned enabled, const float* shading12, float ao_strength, int inverse_ao,
@@ -218,11 +218,13 @@ int isrRecurrentInputBackward(const float* prev_raw, const float* flow, const fl
 
 /* One step of Adam (torch.optim.Adam as mainVideoUnshaded.py:287-289 uses it: betas (0.9, 0.999), eps 1e-8, no weight decay) over
  * FLAT buffers of n floats: params -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps) with the moments updated first;
- * step[0] (device float) = steps taken so far, incremented by the call.  lr_dev (device, may be NULL) overrides lr. */
+ * step[0] (device float) = steps taken so far, incremented by the call.  lr_dev (device, may be NULL) overrides lr.  The betas are
+ * doubles in (0, 1) (else -1): 1 - beta and the bias corrections are formed in double, as torch.optim.Adam forms them. */
 int isrAdamFlatStep(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, const float* lr_dev, float lr,
-                    float beta1, float beta2, float eps, float* step, void* stream);
+                    double beta1, double beta2, float eps, float* step, void* stream);
 
-/* gz = gy * act'(y) for the activations above (y is the post-activation output, before the residual add). */
+/* gz = gy * act'(y) for the activations above (y is the post-activation output, before the residual add).  16-byte accesses where all
+ * three pointers are 16-byte aligned, dword accesses otherwise: the same bits. */
 int isrActBackward(const float* gy, const float* y, float* gz, long long count, int act, float slope, void* stream);
 
 /* Input assembly of one inference frame (replaces inference/loadedmodel.py:84-118,

@@ -23,6 +23,15 @@ namespace {
 // x2 bilinear upsampling
 // ---------------------------------------------------------------------------------------------------------
 // y[p][Y][X] = hy*(hx*x[y0][x0] + lx*x[y0][x1]) + ly*(hx*x[y1][x0] + lx*x[y1][x1])   (ATen's association)
+// The blend and the adjoint's sums are written operation by operation (explicit fmaf, no contraction left to the compiler): the forms
+// below are compiled from different surroundings, and "the same expression" alone got different contractions -- different last bits.
+__device__ __forceinline__ float up2_blend(float hy, float hx, float ly, float lx, float a, float b, float c, float d)
+{
+#pragma clang fp contract(off)
+    const float r0 = fmaf(lx, b, hx * a), r1 = fmaf(lx, d, hx * c);
+    return fmaf(ly, r1, hy * r0);
+}
+
 // V output pixels per thread: 4 where the output rows are whole quads (even w), 2 for an odd w (the rows are whole pairs: W = 2 w)
 template <int V>
 __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w, long long quads)
@@ -44,7 +53,7 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const float* __rest
             int x0, x1; float lx;
             isr_src_index(V * qx + k, 0.5f, w, x0, x1, lx);
             const float hx = 1.f - lx;
-            o[k] = hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
+            o[k] = up2_blend(hy, hx, ly, lx, r0[x0], r0[x1], r1[x0], r1[x1]);
         }
         float* dst = y + (plane * H + Y) * W + V * qx;
         if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
@@ -85,9 +94,9 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const float* __rest
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int X = 2 * ix - 1 + k;
-                if (X >= 0 && X < W) s += wx[k] * row[X];
+                if (X >= 0 && X < W) s = fmaf(wx[k], row[X], s);
             }
-            acc += wy * s;
+            acc = fmaf(wy, s, acc);
         }
         gx[i] = acc;
     }
@@ -96,7 +105,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const float* __rest
 // The same two maps for the shapes of a training step (w a multiple of 4, fewer than 2^31 elements), laid out for the memory system:
 // no 64-bit divisions, the x2 weights in closed form (0.25 / 0.75, 1 at the borders -- what up2_weight evaluates to), a thread per
 // 2 x 4 output block (forward: 12 loads for 8 outputs) / per 4 input pixels (backward: the 4 x 10 window as 8 quad + 8 single loads
-// instead of 64 single ones).  Every output is the same expression in the same order as in the kernels above: same bits.
+// instead of 64 single ones).  Every output is the same operations in the same order as in the kernels above (up2_blend, fmaf sums): same bits.
 __global__ __launch_bounds__(256) void upsample2x_fwd4_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w, unsigned count)
 {
     // a thread = input row iy, input columns 4 q .. 4 q + 3 -> the 2 x 8 output block below them: the 3 x 6 input window is read as
@@ -133,7 +142,7 @@ __global__ __launch_bounds__(256) void upsample2x_fwd4_kernel(const float* __res
             isr_src_index(2 * ix0 + e, 0.5f, w, x0, x1, lx);
             const float hx = 1.f - lx;
             const int c0 = (e + 1) >> 1, c1 = c0 + 1;
-            o[e] = hy * (hx * v[d][c0] + lx * v[d][c1]) + ly * (hx * v[d + 1][c0] + lx * v[d + 1][c1]);
+            o[e] = up2_blend(hy, hx, ly, lx, v[d][c0], v[d][c1], v[d + 1][c0], v[d + 1][c1]);
         }
         *reinterpret_cast<float4*>(dst + (size_t)d * W) = make_float4(o[0], o[1], o[2], o[3]);
         *reinterpret_cast<float4*>(dst + (size_t)d * W + 4) = make_float4(o[4], o[5], o[6], o[7]);
@@ -162,11 +171,11 @@ __global__ __launch_bounds__(256) void upsample2x_bwd4_kernel(const float* __res
         for (int e = 0; e < 4; ++e) {
             const int ix = ix0 + e;
             float s = 0.f;
-            if (ix > 0) s += 0.25f * v[2 * e];
-            s += (ix == 0 ? 1.0f : 0.75f) * v[2 * e + 1];
-            s += (ix == w - 1 ? 1.0f : 0.75f) * v[2 * e + 2];
-            if (ix < w - 1) s += 0.25f * v[2 * e + 3];
-            acc[e] += wy * s;
+            if (ix > 0) s = fmaf(0.25f, v[2 * e], s);
+            s = fmaf(ix == 0 ? 1.0f : 0.75f, v[2 * e + 1], s);
+            s = fmaf(ix == w - 1 ? 1.0f : 0.75f, v[2 * e + 2], s);
+            if (ix < w - 1) s = fmaf(0.25f, v[2 * e + 3], s);
+            acc[e] = fmaf(wy, s, acc[e]);
         }
     }
     *reinterpret_cast<float4*>(gx + ((size_t)plane * h + iy) * w + ix0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -281,10 +290,16 @@ __device__ __forceinline__ void eval_fields(const LossParams& P, const float (&x
     f.m = x[0];
     f.len = sqrtf(x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
     const float den = fmaxf(f.len, 1e-7f);
+    {
+        // The loss takes DIFFERENCES of these products.  Fused into the subtraction (a * gate - round(b * gate) as one fma) a product
+        // leaves its rounding error where a == b, and l1's derivative is the sign of it: a gradient of +-weight / count at a pixel whose
+        // prediction equals the ground truth.  The products are rounded on their own.
+#pragma clang fp contract(off)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { f.nh[k] = x[1 + k] / den; f.n[k] = f.nh[k] * gate; }
-    f.d = x[4] * gate;
-    f.ao = x[5] * gate;
+        for (int k = 0; k < 3; ++k) { f.nh[k] = x[1 + k] / den; f.n[k] = f.nh[k] * gate; }
+        f.d = x[4] * gate;
+        f.ao = x[5] * gate;
+    }
     const float a = P.inverse_ao ? 1.0f - x[5] : x[5];
     f.a_in = a >= 0.f && a <= 1.f;
     f.aof = P.ao_strength * clamp01(a) + (1.0f - P.ao_strength);
@@ -486,10 +501,13 @@ __global__ __launch_bounds__(1024) void loss_finalize_kernel(LossParams P)
     }
 }
 
+bool aligned16(const void* p) { return !(((uintptr_t)p) & 15); }
+
 int fill_loss_params(LossParams& P, const float* gt, const float* pred, const float* prev, int N, int H, int W, int pad,
                      const float* weights15, unsigned enabled, const float* shading12, float ao_strength, int inverse_ao)
 {
     if (!gt || !pred || !weights15 || !shading12 || N <= 0 || H <= 0 || W <= 0 || (W & 3) || pad < 0) return -1;
+    if (!aligned16(gt) || !aligned16(pred) || !aligned16(prev)) return -1;      // the kernels read quads of pixels with 16-byte loads
     if (2 * pad >= H || 2 * pad >= W) return -1;
     P.gt = gt; P.pred = pred; P.prev = prev;
     P.N = N; P.H = H; P.W = W; P.pad = pad;
@@ -668,8 +686,6 @@ bool discr_input_shape_ok(int N, int H, int W, int pad)
 {
     return N > 0 && H > 0 && W > 0 && !(W & 3) && pad >= 0 && 2 * pad < H && 2 * pad < W;
 }
-
-bool aligned16(const void* p) { return !(((uintptr_t)p) & 15); }
 
 // C of the parts that are present, or 0 for a combination no adversarial term has
 int discr_input_channels(bool a, bool b, bool prev)
@@ -921,12 +937,15 @@ __global__ __launch_bounds__(256) void recurrent_input_post_kernel(const RecurPa
 // ---------------------------------------------------------------------------------------------------------
 // Gradient through an activation: gz = gy where y > 0 (or no activation), gy * slope elsewhere (slope 0 for ReLU)
 // ---------------------------------------------------------------------------------------------------------
+// V4: 16-byte accesses (every pointer 16-byte aligned); otherwise the same four elements per thread with dword accesses, as the
+// V2 switch of convt_phase_grad_kernel below
+template <bool V4>
 __global__ void act_backward_kernel(const float* __restrict__ gy, const float* __restrict__ y, float* __restrict__ gz,
                                     long long count, int act, float slope)
 {
     const long long stride = (long long)gridDim.x * blockDim.x * 4;
     for (long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; e < count; e += stride) {
-        if (e + 3 < count) {
+        if (V4 && e + 3 < count) {
             const float4 g = *reinterpret_cast<const float4*>(gy + e);
             const float4 o = *reinterpret_cast<const float4*>(y + e);
             float4 r;
@@ -936,7 +955,8 @@ __global__ void act_backward_kernel(const float* __restrict__ gy, const float* _
             if (act == ISR_ACT_NONE) r = g;
             *reinterpret_cast<float4*>(gz + e) = r;
         } else {
-            for (long long k = e; k < count; ++k) {
+            const long long end = e + 4 < count ? e + 4 : count;
+            for (long long k = e; k < end; ++k) {
                 const float s = act == ISR_ACT_RELU ? 0.f : slope;
                 gz[k] = (act == ISR_ACT_NONE || y[k] > 0.f) ? gy[k] : gy[k] * s;
             }
@@ -989,17 +1009,28 @@ __global__ __launch_bounds__(256) void convt_phase_grad_kernel(const float* __re
 // number of steps taken so far (device, so that a HIP graph replays the right bias corrections); it is read here and
 // incremented by adam_flat_count_kernel afterwards.  lr_dev (may be NULL) overrides lr: a learning rate a scheduler changes
 // between graph replays.
+//
+// The constants arrive as torch.optim.Adam forms them: 1 - beta and the bias corrections in double from the double betas, then rounded
+// once.  (Formed in fp32 from a beta that was rounded to fp32 first, 1 - 0.999f is 1.3e-5 off 0.001 in relative terms and every
+// exp_avg_sq with it, 216 fp32 roundings' worth.)  The bias corrections depend on the device's step counter: the first thread of a
+// workgroup evaluates 1 - beta^t = -expm1(t log beta) in double (lb1 / lb2 = log beta) and shares it.
 __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, long long n, const float* lr_dev, float lr, float b1, float b2,
-                                                         float eps, const float* __restrict__ step)
+                                                         float* __restrict__ v, long long n, const float* lr_dev, float lr, float omb1, float b2,
+                                                         float omb2, double lb1, double lb2, float eps, const float* __restrict__ step)
 {
-    const float t = step[0] + 1.0f;
-    const float bc1 = 1.0f - powf(b1, t), bc2s = sqrtf(1.0f - powf(b2, t));
-    const float step_size = (lr_dev ? lr_dev[0] : lr) / bc1;
+    __shared__ float shared[2];
+    if (threadIdx.x == 0) {
+        const double t = (double)step[0] + 1.0;
+        const double bc1 = -expm1(t * lb1), bc2 = -expm1(t * lb2);
+        shared[0] = (float)((double)(lr_dev ? lr_dev[0] : lr) / bc1);
+        shared[1] = (float)sqrt(bc2);
+    }
+    __syncthreads();
+    const float step_size = shared[0], bc2s = shared[1];
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);                  // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;                // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        const float mi = m[i] + (gi - m[i]) * omb1;                         // exp_avg.lerp_(grad, 1 - beta1)
+        const float vi = v[i] * b2 + omb2 * gi * gi;                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
         m[i] = mi; v[i] = vi;
         p[i] -= step_size * (mi / (sqrtf(vi) / bc2s + eps));
     }
@@ -1016,17 +1047,21 @@ int isrActBackward(const float* gy, const float* y, float* gz, long long count, 
     long long blocks = (count / 4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(act_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, gy, y, gz, count, act, slope);
+    const bool v4 = !(((uintptr_t)gy | (uintptr_t)y | (uintptr_t)gz) & 15);
+    hipLaunchKernelGGL(v4 ? act_backward_kernel<true> : act_backward_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       gy, y, gz, count, act, slope);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int isrAdamFlatStep(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, const float* lr_dev, float lr,
-                    float beta1, float beta2, float eps, float* step, void* stream)
+                    double beta1, double beta2, float eps, float* step, void* stream)
 {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !step || n <= 0) return -1;
+    if (!(beta1 > 0.0 && beta1 < 1.0 && beta2 > 0.0 && beta2 < 1.0)) return -1;
     const long long blocks = (n + 255) / 256;
     hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, (hipStream_t)stream,
-                       params, grads, exp_avg, exp_avg_sq, n, lr_dev, lr, beta1, beta2, eps, (const float*)step);
+                       params, grads, exp_avg, exp_avg_sq, n, lr_dev, lr, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), log(beta1), log(beta2),
+                       eps, (const float*)step);
     hipLaunchKernelGGL(adam_flat_count_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -1088,7 +1123,7 @@ int isrLossUnshadedBackward(const float* gt, const float* pred, const float* pre
                             const float* gvalues16, float* gpred, float* gprev, void* stream)
 {
     LossParams P;
-    if (!gvalues16 || !gpred) return -1;
+    if (!gvalues16 || !gpred || !aligned16(gpred) || !aligned16(gprev)) return -1;
     if (gprev && !prev) return -1;
     if (int rc = fill_loss_params(P, gt, pred, prev, N, H, W, pad, weights15, enabled, shading12, ao_strength, inverse_ao)) return rc;
     P.gout = gvalues16; P.gpred = gpred; P.gprev = gprev;

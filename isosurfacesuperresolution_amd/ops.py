@@ -161,7 +161,7 @@ def _bind(lib):
     lib.isrResBlockSplitWorkspaceBytes.argtypes = []; lib.isrResBlockSplitWorkspaceBytes.restype = ll
     lib.isrResBlockSplitSupported.argtypes = [vp, ci, ci, ll, ll]; lib.isrResBlockSplitSupported.restype = ci
     lib.isrResBlockSplit.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ll, ll, vp]; lib.isrResBlockSplit.restype = ci
-    lib.isrAdamFlatStep.argtypes = [vp, vp, vp, vp, ll, vp, cf, cf, cf, cf, vp, vp]; lib.isrAdamFlatStep.restype = ci
+    lib.isrAdamFlatStep.argtypes = [vp, vp, vp, vp, ll, vp, cf, ctypes.c_double, ctypes.c_double, cf, vp, vp]; lib.isrAdamFlatStep.restype = ci
     lib.isrSetRangeFlag.argtypes = [vp]; lib.isrSetRangeFlag.restype = None
     lib.isrSetTrunkErrorWord.argtypes = [vp]; lib.isrSetTrunkErrorWord.restype = None
     lib.isrSetTrunkRows.argtypes = [ci]; lib.isrSetTrunkRows.restype = None
@@ -2020,6 +2020,12 @@ def recurrent_input_supported(prev_raw, input_low, flow_low, upscale):
             and prev_raw.shape[2] == 4 * input_low.shape[2] and prev_raw.shape[3] == 4 * input_low.shape[3])
 
 
+def _aligned16(t):
+    """``t`` (contiguous, or None) at a 16-byte aligned address: itself, or a copy where it is a view at an odd storage offset --
+    ``.contiguous()`` keeps such a view as it is, and the loss kernels read quads of pixels with 16-byte loads."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 LOSS_KINDS = ('mse', 'l1', 'temp-l2')
 LOSS_TARGETS = ('mask', 'normal', 'ao', 'depth', 'color')
 _loss_ws = {}
@@ -2031,8 +2037,8 @@ class _LossUnshadedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gt, pred, prev, cfg):
         lib = _sr()
-        gt, pred = gt.contiguous(), pred.contiguous()
-        prev = prev.contiguous() if prev is not None else None
+        gt, pred = _aligned16(gt.contiguous()), _aligned16(pred.contiguous())
+        prev = _aligned16(prev.contiguous()) if prev is not None else None
         n, _, h, w = pred.shape
         key = (pred.device, torch.cuda.current_stream().cuda_stream)
         ws = _loss_ws.get(key)

@@ -127,3 +127,35 @@ def operands(combination, n, h, w, padding, seed=7):
     input = C.uniform(seed + 2, n, 5, h, w) if has_input else None
     prev_input = C.uniform(seed + 3, n, 5, h, w) if has_prev_input else None
     return (cur, prev, input, prev_input), planted
+
+
+def pixel_sets(planted, n, h, w, padding):
+    inside = torch.zeros(n, h, w, dtype=torch.bool)
+    if 2 * padding < min(h, w):
+        inside[:, padding:h - padding, padding:w - padding] = True
+    any_planted = torch.zeros(n, h, w, dtype=torch.bool)
+    for m in planted.values():
+        any_planted |= m
+    return dict(planted, rest=inside & ~any_planted), ~inside
+
+
+def compare(label, got, ref64, ref32, sets, border, relative, floor, record=None):
+    """The comparison rule of the element-wise training kernels' tests (test_discr_input_gpu.py, test_train_pointwise_gpu.py).  Per pixel set: the largest |got - fp64| against max(4 x largest |fp32 - fp64|, floor), both relative to the set's largest |fp64|
+    for a gradient (``relative``); border pixels exactly 0.  -> the sets that miss.  ``record(label, kind, error, own, bar)`` is called
+    for every set, if given."""
+    at = lambda t, m: t.permute(0, 2, 3, 1)[m]
+    assert not at(got, border).any(), "%s: a border pixel is not 0" % label
+    bad = []
+    for kind, m in sets.items():
+        if not m.any():
+            continue
+        r = at(ref64, m)
+        scale = float(r.abs().max()) if relative else 1.0
+        err, own = float((at(got, m).double() - r).abs().max()), float((at(ref32, m) - r).abs().max())
+        bar = max(4.0 * own, floor * scale)
+        print("%-34s %-14s error %.3e  fp32-vs-fp64 %.3e  bar %.3e  (largest |value| %.3e)" % (label, kind, err, own, bar, float(r.abs().max())))
+        if record is not None:
+            record(label, kind, err, own, bar)
+        if not err <= bar:
+            bad.append((label, kind, err, bar))
+    return bad

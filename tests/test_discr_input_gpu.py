@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import gan_common as C
-from discr_input_common import CHANNELS, CLEAR, COMBINATIONS, composition, kink_clearance, make_shading, operands
+from discr_input_common import CHANNELS, CLEAR, COMBINATIONS, compare, composition, kink_clearance, make_shading, operands, pixel_sets
 from isosurfacesuperresolution_amd import ops
 from train_route_common import observed
 
@@ -49,35 +49,6 @@ def run_device(tensors, gout, padding, order, raw, inverse_ao, ao):
     g = gout.cuda()
     _, _, bwd_names = observed(lambda: out.backward(g))
     return (out.detach().cpu(), cur.grad.cpu(), prev.grad.cpu() if prev is not None else None), fwd_names, bwd_names
-
-
-def pixel_sets(planted, n, h, w, padding):
-    inside = torch.zeros(n, h, w, dtype=torch.bool)
-    if 2 * padding < min(h, w):
-        inside[:, padding:h - padding, padding:w - padding] = True
-    any_planted = torch.zeros(n, h, w, dtype=torch.bool)
-    for m in planted.values():
-        any_planted |= m
-    return dict(planted, rest=inside & ~any_planted), ~inside
-
-
-def compare(label, got, ref64, ref32, sets, border, relative, floor):
-    """Per pixel set: the largest |got - fp64| against max(4 x largest |fp32 - fp64|, floor), both relative to the set's largest |fp64|
-    for a gradient (``relative``); border pixels exactly 0.  -> the sets that miss."""
-    at = lambda t, m: t.permute(0, 2, 3, 1)[m]
-    assert not at(got, border).any(), "%s: a border pixel is not 0" % label
-    bad = []
-    for kind, m in sets.items():
-        if not m.any():
-            continue
-        r = at(ref64, m)
-        scale = float(r.abs().max()) if relative else 1.0
-        err, own = float((at(got, m).double() - r).abs().max()), float((at(ref32, m) - r).abs().max())
-        bar = max(4.0 * own, floor * scale)
-        print("%-34s %-14s error %.3e  fp32-vs-fp64 %.3e  bar %.3e  (largest |value| %.3e)" % (label, kind, err, own, bar, float(r.abs().max())))
-        if not err <= bar:
-            bad.append((label, kind, err, bar))
-    return bad
 
 
 def check_shape(combination, n, h, w, padding, variants, expect_kernels):
