@@ -676,6 +676,34 @@ int isrShuffleTailDataGrad(const float* dout, long long doutPlane, long long dou
 int isrShuffleTailWeightGrad(const float* dout, long long doutPlane, long long doutImage, const float* f, long long fPlane, long long fImage,
                              int N, int C, int Cout, int h, int w, int tiles, double* workspace, float* dWeight, float* dBias, void* stream);
 
+/* Training-mode batch normalisation of the EnhanceNet blocks (csrc/sr_batchnorm.hip; an eval-mode layer is folded into its convolution
+ * on the host side and launches nothing).  x, y, dy, dx, residual: fp32 [N][C][H][W], packed; M = N H W >= 2 values per channel, any
+ * C, H, W >= 1, N and C <= 65535 (isrBatchNormSupported says so beforehand: anything else returns -3).  Returns as above.  16-byte
+ * accesses where every base address is a multiple of 16 bytes and H W a multiple of four, a per-element path otherwise.  Every sum is
+ * taken in fp64 in a fixed order, without floating-point atomics and without host synchronisation: a result depends on the shape only,
+ * and the launches can be captured in a graph.
+ *   isrBatchNormStats: TWO launches.  Slab sums of x - k and (x - k)^2 (k: the channel's first value) -> workspace
+ *     double [C][N S][2], S = isrBatchNormSlabs(N, C, H, W) slabs per plane; then one thread per channel: the partials in index order,
+ *     mean[c], invstd[c] = 1 / sqrt(var + eps) with the BIASED variance, both rounded to fp32 once, and -- where the pointers are not
+ *     NULL -- running = (1 - momentum) running + momentum {mean, var M / (M - 1)} in place, exactly once per call.
+ *   isrBatchNormApply: ONE launch.  y = ((x - mean) * invstd) * gamma + beta with every operation rounded separately, then ReLU (`relu`)
+ *     and / or + residual (NULL: none).
+ *   isrBatchNormGradSums: TWO launches.  With g = dy where y > 0 and 0 elsewhere (y: the output of the ReLU form; NULL: g = dy) and
+ *     xhat = (x - mean) * invstd: slab sums of g and g xhat -> workspace (as above), then dBeta[c] = sum g, dGamma[c] = sum g xhat (either
+ *     may be NULL) and coef[c] = {sum g / M, sum g xhat / M} as fp32.
+ *   isrBatchNormBackward: ONE launch.  dx = ((g - coef[c][0]) - xhat * coef[c][1]) * (gamma * invstd).  (The gradient of the residual
+ *     IS dy: no entry point.) */
+int isrBatchNormSupported(int N, int C, int H, int W);
+int isrBatchNormSlabs(int N, int C, int H, int W);
+int isrBatchNormStats(const float* x, int N, int C, int H, int W, int S, double* workspace, double eps, double momentum, float* mean,
+                      float* invstd, float* runningMean, float* runningVar, void* stream);
+int isrBatchNormApply(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, const float* residual,
+                      int relu, float* y, int N, int C, int H, int W, void* stream);
+int isrBatchNormGradSums(const float* dy, const float* x, const float* y, const float* mean, const float* invstd, int N, int C, int H, int W,
+                         int S, double* workspace, float* coef, float* dGamma, float* dBeta, void* stream);
+int isrBatchNormBackward(const float* dy, const float* x, const float* y, const float* mean, const float* invstd, const float* gamma,
+                         const float* coef, float* dx, int N, int C, int H, int W, void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

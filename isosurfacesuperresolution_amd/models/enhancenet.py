@@ -8,7 +8,9 @@ Same constructor, attributes, sub-module names and ``state_dict`` keys as
 of conv -> activation -> add as separate library calls.
 
 Architecture (enhancenet.py:92-125): pre: conv(Cin->64)+ReLU; 10 x [conv+ReLU, conv] with
-skip; post: up x2, conv+ReLU, up x2, conv+ReLU, conv+ReLU, conv(64->Cout).  Reconstruction
+skip (``useBN``: [conv, BatchNorm2d, ReLU, conv, BatchNorm2d], keys ``blocks.{0..9}.{0,1,3,4}``: in eval mode the batch-norm layers
+are folded into their convolutions and the net runs as a plain one, in training mode they run ``ops.batch_norm``); post: up x2,
+conv+ReLU, up x2, conv+ReLU, conv+ReLU, conv(64->Cout).  Reconstruction
 (``:51-90``): with ``reconType='residual'`` the first ``len(channel_mask)`` output channels get
 the bilinearly resized first ``len(channel_mask)`` input channels added (sliced, not gathered).
 Initialisation (``:127-133``): orthogonal with gain sqrt(2) for the convs inside ``blocks`` only.
@@ -82,12 +84,26 @@ class EnhanceNet(nn.Module):
         return torch.cat([resized + outputs[:, 0:k], outputs[:, k:]], dim=1), outputs
 
     def _fused_ok(self):
-        return (not self.use_bn) and self.upsample == 'bilinear'
+        return self.upsample == 'bilinear'
+
+    def _bn_live(self, inputs=None):
+        """A batch-norm net whose layers cannot be folded into their convolutions: training mode (batch statistics), or eval mode with
+        a gradient required (the folded tensors carry none)."""
+        if not self.use_bn:
+            return False
+        if self.training:
+            return True
+        return torch.is_grad_enabled() and ((inputs is not None and inputs.requires_grad) or any(p.requires_grad for p in self.parameters()))
 
     def trunk_convs(self):
-        """[(weight, bias)] of the low-resolution trunk: preblock, then conv1 / conv2 of every block (what ops.trunk_supported takes)."""
+        """[(weight, bias)] of the low-resolution trunk: preblock, then conv1 / conv2 of every block (what ops.trunk_supported takes).
+        A batch-norm net in eval mode: every block convolution with its batch-norm layer folded in (``ops.fold_batch_norm``: persistent
+        tensors, refreshed in place when a source changed) -- from here on it is a plain net."""
         pre = self.preblock[0]
-        return [(pre.weight, pre.bias)] + [(m.weight, m.bias) for block in self.blocks for m in (block[0], block[2])]
+        if self.use_bn and not self.training:
+            return [(pre.weight, pre.bias)] + [ops.fold_batch_norm(block[i].weight, block[i].bias, block[i + 1])
+                                               for block in self.blocks for i in (0, 3)]
+        return [(pre.weight, pre.bias)] + [(m.weight, m.bias) for block in self.blocks for m in (block[0], block[3 if self.use_bn else 2])]
 
     def forward_features(self, inputs, last_layer=True, last_two=True, last_three=True, after_trunk=None, packed_tail=False):
         """The convolutional trunk only: the tensor ``_recon_image`` receives (used by the fused
@@ -102,16 +118,26 @@ class EnhanceNet(nn.Module):
         assert self._fused_ok()
         c = ops.conv3x3
         pre = self.preblock[0]
-        convs = self.trunk_convs()
-        if ops.trunk_supported(inputs, convs):
-            f = ops.trunk_dataflow(inputs, convs)       # preblock + all blocks in ONE dataflow launch (csrc/sr_conv_trunk.hip)
-        elif getattr(inputs, '_isr_prepacked', None) is not None:
-            raise RuntimeError("forward_features: this input exists only packed-split inside the dataflow trunk's workspace "
-                               "(ops.assemble_input_packed) and the dataflow trunk does not take it; assemble it with ops.assemble_input")
-        else:
+        if self._bn_live(inputs):
+            # batch statistics (or an eval-mode layer that has to pass a gradient on): per layer, conv -> ops.batch_norm; three launches
+            # forward and three backward per batch-norm layer (csrc/sr_batchnorm.hip), the skip added by the second one's streaming pass
+            if getattr(inputs, '_isr_prepacked', None) is not None:
+                raise RuntimeError("forward_features: a packed-split input is the dataflow trunk's; a batch-norm net with live layers runs per layer")
             f = c(inputs, pre.weight, pre.bias, act='relu')
             for block in self.blocks:
-                f = ops.residual_block(f, block[0].weight, block[0].bias, block[2].weight, block[2].bias)
+                t = ops.batch_norm(c(f, block[0].weight, block[0].bias), block[1], act='relu')
+                f = ops.batch_norm(c(t, block[3].weight, block[3].bias), block[4], residual=f)
+        else:
+            convs = self.trunk_convs()
+            if ops.trunk_supported(inputs, convs):
+                f = ops.trunk_dataflow(inputs, convs)       # preblock + all blocks in ONE dataflow launch (csrc/sr_conv_trunk.hip)
+            elif getattr(inputs, '_isr_prepacked', None) is not None:
+                raise RuntimeError("forward_features: this input exists only packed-split inside the dataflow trunk's workspace "
+                                   "(ops.assemble_input_packed) and the dataflow trunk does not take it; assemble it with ops.assemble_input")
+            else:
+                f = c(inputs, pre.weight, pre.bias, act='relu')
+                for i in range(1, len(convs), 2):
+                    f = ops.residual_block(f, convs[i][0], convs[i][1], convs[i + 1][0], convs[i + 1][1])
         if after_trunk is not None:
             after_trunk()
         p = self.postblock

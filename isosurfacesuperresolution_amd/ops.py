@@ -218,6 +218,14 @@ def _bind(lib):
         lib.isrShuffleTailGradTiles.argtypes = [ci, ci, ci]; lib.isrShuffleTailGradTiles.restype = ci
         lib.isrShuffleTailDataGrad.argtypes = [vp, ll, ll, vp, vp, ll, ll, ci, ci, ci, ci, ci, vp]; lib.isrShuffleTailDataGrad.restype = ci
         lib.isrShuffleTailWeightGrad.argtypes = [vp, ll, ll, vp, ll, ll, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]; lib.isrShuffleTailWeightGrad.restype = ci
+    if hasattr(lib, "isrBatchNormStats"):                       # (likewise: training-mode batch normalisation, csrc/sr_batchnorm.hip)
+        cd = ctypes.c_double
+        lib.isrBatchNormSupported.argtypes = [ci, ci, ci, ci]; lib.isrBatchNormSupported.restype = ci
+        lib.isrBatchNormSlabs.argtypes = [ci, ci, ci, ci]; lib.isrBatchNormSlabs.restype = ci
+        lib.isrBatchNormStats.argtypes = [vp, ci, ci, ci, ci, ci, vp, cd, cd, vp, vp, vp, vp, vp]; lib.isrBatchNormStats.restype = ci
+        lib.isrBatchNormApply.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, vp]; lib.isrBatchNormApply.restype = ci
+        lib.isrBatchNormGradSums.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]; lib.isrBatchNormGradSums.restype = ci
+        lib.isrBatchNormBackward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]; lib.isrBatchNormBackward.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -423,7 +431,10 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  # the stride-2 convolution of the discriminators (csrc/sr_conv_stride2.hip)
                  48: "conv3x3s2_fwd_kernel", 49: "conv3x3s2_dgrad_kernel", 50: "conv3x3s2_wgrad_kernel", 51: "conv3x3s2_wgrad_sum_kernel",
                  # the discriminator inputs of the adversarial terms (csrc/sr_train.hip)
-                 52: "discr_input_fwd_kernel", 53: "discr_input_bwd_kernel"}
+                 52: "discr_input_fwd_kernel", 53: "discr_input_bwd_kernel",
+                 # training-mode batch normalisation (csrc/sr_batchnorm.hip): forward 54-56, backward 57-59
+                 54: "batch_norm_stat_kernel", 55: "batch_norm_finish_kernel", 56: "batch_norm_apply_kernel",
+                 57: "batch_norm_grad_sum_kernel", 58: "batch_norm_grad_finish_kernel", 59: "batch_norm_backward_kernel"}
 
 
 def debug_switches():
@@ -3047,6 +3058,188 @@ class _PixelShuffle4ConvFunction(torch.autograd.Function):
             if rc != 0:
                 raise RuntimeError("isrShuffleTailWeightGrad failed (%d)" % rc)
         return df, dw if need[1] else None, db if (ctx.has_bias and need[2]) else None
+
+
+# ---- batch normalisation of the EnhanceNet blocks (models/enhancenet.py with use_bn; csrc/sr_batchnorm.hip) ---------------------------
+# Two halves.  In eval mode a layer is an affine map per channel: ``fold_batch_norm`` folds it into the convolution in front of it and
+# the network IS a plain EnhanceNet -- every fused route applies, nothing new is launched.  In training mode ``batch_norm`` is ONE
+# autograd node on the kernels of csrc/sr_batchnorm.hip: three launches forward (slab sums, the once-only finishing step, the streaming
+# pass), three backward; sums in fp64 in a fixed order, so a call repeats bit for bit; no host read, so the call can be captured.
+# False: ``batch_norm`` is the ``nn.BatchNorm2d`` module itself on the device without a word (tools/bench_bn_train.py's comparison and the
+# tests' A/B).  A MEASUREMENT switch.
+BATCH_NORM_KERNELS = True
+_fold_cache = weakref.WeakKeyDictionary()          # bn module -> [weakref(conv weight), stamps of the six sources, epoch, weight', bias']
+
+
+def _bn_shape_ok(x, bn):
+    return torch.is_tensor(x) and x.dim() == 4 and x.shape[1] == bn.num_features and x.numel() > 0
+
+
+def batch_norm_supported(x, bn):
+    """Does ``batch_norm(x, bn)`` run the HIP kernels?  A training-mode ``nn.BatchNorm2d`` with a fixed momentum, affine parameters and
+    running statistics, all fp32 on the device of the fp32 tensor x [N, C, H, W] with N H W >= 2.  Everything else -- the CPU, eval
+    mode, ``momentum=None``, ``affine=False``, ``track_running_stats=False``, another dtype -- is the ``F.batch_norm`` composition."""
+    if not (BATCH_NORM_KERNELS and bn.training and _bn_shape_ok(x, bn) and x.is_cuda and x.dtype == torch.float32):
+        return False
+    if bn.momentum is None or not bn.affine or not bn.track_running_stats or bn.running_mean is None:
+        return False
+    if not all(t.dtype == torch.float32 and t.device == x.device and t.is_contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+        return False
+    n, c, h, w = x.shape
+    lib = _sr()
+    return hasattr(lib, "isrBatchNormStats") and bool(lib.isrBatchNormSupported(n, c, h, w))
+
+
+def _batch_norm_torch(x, bn, act, residual):
+    # nn.BatchNorm2d.forward: F.batch_norm and the bookkeeping around it.  On the device ATen's own kernels, not the vendor library's:
+    # that one takes the variance in one fp32 pass and is 1.5e-5 of max|y| off where a channel's mean is large against its spread
+    # (tests/test_bn_gpu.py), ATen's (Welford) stay within the bars of the HIP kernels.
+    vendor = torch.backends.cudnn.enabled
+    if x.is_cuda:
+        torch.backends.cudnn.enabled = False
+    try:
+        y = bn(x)
+    finally:
+        torch.backends.cudnn.enabled = vendor
+    if act == 'relu':
+        y = F.relu(y)
+    return y + residual if residual is not None else y
+
+
+def _batch_norm_forward(x, bn, weight, bias, relu, residual):
+    """The three forward launches -> (y, x as the kernels read it, mean, invstd); the running statistics are updated in place."""
+    lib = _sr()
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    res = residual.contiguous() if residual is not None else None
+    slabs = lib.isrBatchNormSlabs(n, c, h, w)
+    ws = torch.empty(2 * c * n * slabs, dtype=torch.float64, device=x.device)
+    mean, invstd = torch.empty((2, c), dtype=torch.float32, device=x.device).unbind(0)
+    y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    rc = lib.isrBatchNormStats(_ptr(x), n, c, h, w, slabs, _ptr(ws), float(bn.eps), float(bn.momentum), _ptr(mean), _ptr(invstd),
+                               _ptr(bn.running_mean), _ptr(bn.running_var), _stream())
+    if rc != 0:
+        raise RuntimeError("isrBatchNormStats failed (%d)" % rc)
+    # (the kernel wrote the two buffers through their addresses: their version counters say so to whoever keys on them -- fold_batch_norm)
+    torch.autograd.graph.increment_version(bn.running_mean)
+    torch.autograd.graph.increment_version(bn.running_var)
+    rc = lib.isrBatchNormApply(_ptr(x), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(bias), _ptr(res), 1 if relu else 0, _ptr(y), n, c, h, w,
+                               _stream())
+    if rc != 0:
+        raise RuntimeError("isrBatchNormApply failed (%d)" % rc)
+    return y, x, mean, invstd
+
+
+class _BatchNormFunction(torch.autograd.Function):
+    """act(batch_norm(x)) + residual as ONE autograd node: the three forward launches of the no-grad route; x, mean, invstd (and y for
+    the ReLU form, whose sign gates dy) are saved.  Backward: ``isrBatchNormGradSums`` (two launches: slab sums, then dgamma, dbeta and
+    the streaming pass's coefficients), ``isrBatchNormBackward`` only if x needs a gradient; the residual's gradient IS dy."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, bn, relu):
+        y, x, mean, invstd = _batch_norm_forward(x, bn, weight, bias, relu, residual)
+        ctx.relu = relu
+        ctx.save_for_backward(x, y if relu else None, mean, invstd, weight)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, y, mean, invstd, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gres = gy if need[3] else None
+        if not any(need[0:3]):
+            return None, None, None, gres, None, None
+        lib = _sr()
+        n, c, h, w = x.shape
+        g = gy.contiguous()
+        slabs = lib.isrBatchNormSlabs(n, c, h, w)
+        ws = torch.empty(2 * c * n * slabs, dtype=torch.float64, device=x.device)
+        coef = torch.empty(2 * c, dtype=torch.float32, device=x.device)
+        dgamma = torch.empty(c, dtype=torch.float32, device=x.device) if need[1] else None
+        dbeta = torch.empty(c, dtype=torch.float32, device=x.device) if need[2] else None
+        rc = lib.isrBatchNormGradSums(_ptr(g), _ptr(x), _ptr(y), _ptr(mean), _ptr(invstd), n, c, h, w, slabs, _ptr(ws), _ptr(coef),
+                                      _ptr(dgamma), _ptr(dbeta), _stream())
+        if rc != 0:
+            raise RuntimeError("isrBatchNormGradSums failed (%d)" % rc)
+        dx = None
+        if need[0]:
+            dx = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+            rc = lib.isrBatchNormBackward(_ptr(g), _ptr(x), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(weight), _ptr(coef), _ptr(dx), n, c, h, w,
+                                          _stream())
+            if rc != 0:
+                raise RuntimeError("isrBatchNormBackward failed (%d)" % rc)
+        return dx, dgamma, dbeta, gres, None, None
+
+
+def batch_norm(x, bn, act='none', residual=None):
+    """``act(bn(x)) + residual`` for an ``nn.BatchNorm2d`` -- the two combinations of an EnhanceNet block: act='relu' without a residual
+    (the first layer of a block), no activation plus the block's skip (the second).  A training-mode layer on the device: the kernels
+    of csrc/sr_batchnorm.hip (``batch_norm_supported``), forward-only under ``no_grad``; batch statistics with the biased variance, the
+    running statistics updated once, in place, with the unbiased one, ``num_batches_tracked += 1`` as the torch op it is.  On the CPU
+    the ``F.batch_norm`` composition IS the definition; on the device it is what runs -- after a warning, once -- where the kernels do
+    not apply.  One value per channel in training mode raises ``ValueError``, as PyTorch does."""
+    if act not in ('none', 'relu'):
+        raise ValueError("batch_norm: unknown activation %r" % (act,))
+    if act == 'relu' and residual is not None:
+        raise ValueError("batch_norm: an activation together with a residual is not a combination of the blocks")
+    if not _bn_shape_ok(x, bn):
+        raise ValueError("batch_norm: expected a [N, %d, H, W] tensor, got %s" % (bn.num_features, tuple(x.shape)))
+    if bn.training and x.numel() // x.shape[1] < 2:
+        raise ValueError("batch_norm: expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    if not x.is_cuda or not BATCH_NORM_KERNELS:
+        return _batch_norm_torch(x, bn, act, residual)
+    if not batch_norm_supported(x, bn):
+        _warn_once("batch_norm", "batch_norm: the HIP kernels take a training-mode fp32 layer with momentum, affine parameters and running "
+                   "statistics; F.batch_norm runs instead (%s, training=%s)" % (tuple(x.shape), bn.training))
+        return _batch_norm_torch(x, bn, act, residual)
+    if residual is not None and (residual.shape != x.shape or residual.dtype != torch.float32 or residual.device != x.device):
+        raise ValueError("batch_norm: the residual must be an fp32 tensor of x's shape on x's device")
+    if _any_requires_grad(x, bn.weight, bn.bias, residual):
+        y = _BatchNormFunction.apply(x, bn.weight, bn.bias, residual, bn, act == 'relu')
+    else:
+        with torch.no_grad():
+            y = _batch_norm_forward(x, bn, bn.weight, bn.bias, act == 'relu', residual)[0]
+            y._isr_range_key = HOT                   # nobody watched its range: its consumer takes the exact kernels
+    if bn.num_batches_tracked is not None:
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+    return y
+
+
+def _fold_sources(weight, bias, bn):
+    return (weight, bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+
+
+def fold_batch_norm(weight, bias, bn):
+    """The convolution an eval-mode ``bn`` behind conv(weight, bias) amounts to -> (weight', bias'), computed in fp64 on the tensors'
+    device and rounded to fp32 once: s = gamma / sqrt(running_var + eps), weight' = weight * s[co], bias' = (bias - running_mean) * s
+    + beta.  The results are PERSISTENT tensors per layer, rewritten IN PLACE when a source changes, so every image cache downstream
+    (``_wcache``, the split images, the dataflow trunk's table) sees an ordinary weight that was updated.  Staleness is the rule of
+    ``_WeightImages``: the (_version, data_ptr) of each of the six sources and ``_images_epoch`` -- a graph replay moves the running
+    statistics without advancing ``_version``, and ``train.GraphedTrainStep`` calls ``invalidate_weight_images()`` after each."""
+    if bn.running_mean is None or bn.running_var is None:
+        raise ValueError("fold_batch_norm: the layer tracks no running statistics; there is nothing to fold")
+    sources = _fold_sources(weight, bias, bn)
+    stamp = _WeightImages._stamp(sources)
+    hit = _fold_cache.get(bn)
+    if hit is not None and hit[0]() is weight and hit[1] == stamp and hit[2] == _images_epoch:
+        return hit[3], hit[4]
+    with torch.no_grad():
+        var = bn.running_var.detach().double()
+        s = torch.rsqrt(var + bn.eps) if bn.weight is None else bn.weight.detach().double() / torch.sqrt(var + bn.eps)
+        w = (weight.detach().double() * s[:, None, None, None]).float()
+        b = -bn.running_mean.detach().double() if bias is None else bias.detach().double() - bn.running_mean.detach().double()
+        b = b * s
+        if bn.bias is not None:
+            b = b + bn.bias.detach().double()
+        b = b.float()
+        if hit is not None and hit[0]() is weight and hit[3].shape == w.shape and hit[3].device == w.device:
+            hit[3].copy_(w); hit[4].copy_(b)          # in place: the tensors' _version moves, their consumers' images follow
+            hit[1], hit[2] = stamp, _images_epoch
+            return hit[3], hit[4]
+    _fold_cache[bn] = [weakref.ref(weight), stamp, _images_epoch, w, b]
+    return w, b
 
 
 # ---- the viewer's display stage (viewer.py) --------------------------------------------------------------------------------------------

@@ -145,7 +145,8 @@ def is_colour(model):
 
 def fused_path_ok(model, upscale=4):
     """The fused frame kernels take this network: 4x, residual reconstruction over the five input channels -- or, a colour model, over
-    [0, 1, 2] with three outputs, bilinear upsampling and no batch norm (EnhanceNet) / a last convolution 64 -> 3 (TecoGAN); a colour
+    [0, 1, 2] with three outputs and bilinear upsampling (EnhanceNet; with batch norm too: in eval mode its layers are folded into their
+    convolutions, ``ops.fold_batch_norm``) / a last convolution 64 -> 3 (TecoGAN); a colour
     RCAN (no reconstruction type to ask for) with mask [0, 1, 2] and a last convolution 4 -> 3."""
     net = model.model
     if isinstance(net, RCAN):
@@ -162,7 +163,7 @@ def fused_path_ok(model, upscale=4):
             and (last.in_channels, last.out_channels) == (64, 3) and model.input_channels - 48 in ops.COLOUR_VARIANTS
     if is_colour(model):
         return list(net.channel_mask) == [0, 1, 2] and getattr(net, 'output_channels', None) == 3 \
-            and getattr(net, 'upsample', None) == 'bilinear' and not getattr(net, 'use_bn', True) and hasattr(net, 'forward_features') \
+            and getattr(net, 'upsample', None) == 'bilinear' and hasattr(net, 'forward_features') \
             and model.input_channels - 48 in ops.COLOUR_VARIANTS
     return len(net.channel_mask) == 5
 
@@ -172,7 +173,8 @@ class SuperResolutionPipeline:
         """``graph`` (default: ISR_FRAME_GRAPH=1): steady-state frames -- temporal sequence, next frame's camera known -- replay as
         ONE HIP graph per frame (``_frame_graph``).  The returned tensors are then the pipeline's static output buffers: valid
         until the frame after next overwrites them.  NOT for colour models: the graph's static buffers are the unshaded networks'
-        six-channel ones, so with a colour model ``graph`` is switched off and every frame runs eagerly.
+        six-channel ones, so with a colour model ``graph`` is switched off and every frame runs eagerly.  Nor for batch-norm models:
+        the graph's validity signature does not cover the batch-norm parameters and running statistics the folded convolutions are made of.
 
         Colour models (``model.unshaded == False``; RGB in, RGB out): ``frame`` returns ``(rgb, raw)`` with BOTH [1,3,4h,4w] and the
         same values -- the prediction clamped to [0, 1], which is the displayed image and ``self.previous`` (mainVideo.py:416);
@@ -232,6 +234,8 @@ class SuperResolutionPipeline:
         # ---- the frame as one HIP graph ------------------------------------------------------------------------
         self.graph = (os.environ.get("ISR_FRAME_GRAPH", "0") == "1") if graph is None else bool(graph)
         self.graph = self.graph and self.fused and self._render_stream is not None and not self.colour
+        # NOT for batch-norm models either: the graph's validity signature does not cover the sources of the folded convolutions
+        self.graph = self.graph and not getattr(model.model, 'use_bn', False)
         self._graphs = [None, None]       # per G-buffer slot: the frame whose G-buffer sits in slot s (and renders the next one into s ^ 1)
         self._graph_sig = None
         self._graph_pool = None

@@ -646,7 +646,10 @@ class DataParallelTrainer:
     (autograd adds in place into an existing ``.grad``; the deferred weight-gradient pass does ``grad.add_``), so the
     exchange is ONE ``all_reduce`` + ONE ``div_`` and zeroing the gradients ONE ``zero_`` -- no per-parameter copies
     around a 42 us collective.  Nothing may replace ``param.grad`` afterwards: use ``trainer.zero_grad()``, never
-    ``optimizer.zero_grad()`` (whose default sets the gradients to None)."""
+    ``optimizer.zero_grad()`` (whose default sets the gradients to None).
+
+    A batch-norm generator (``useBN``): batch statistics and running statistics are PER RANK and not synchronised -- every rank
+    normalises with its own shard's statistics and keeps its own running mean and variance; only the gradients are exchanged."""
 
     def __init__(self, model, criterion, optimizer, process_group=None):
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
