@@ -32,7 +32,7 @@ from . import ops
 from .inference.flowfill import fill_flow
 from .models import VideoTools
 from .pipeline import fused_path_ok, run_network
-from .utils import ScreenSpaceShading, initialImage
+from .utils import clamp_prediction, initialImage
 
 HALO = 24
 
@@ -158,10 +158,7 @@ class StripSuperResolution:
         raw, _ = net._recon_image(xs, net.forward_features(xs))
         if after_trunk is not None:
             after_trunk()
-        raw = torch.cat([torch.clamp(raw[:, 0:1], -1, +1),
-                         ScreenSpaceShading.normalize(raw[:, 1:4], dim=1),
-                         torch.clamp(raw[:, 4:], 0, 1)], dim=1)
-        raw = raw[:, :, (y0 - e0) * u:(y1 - e0) * u, (x0 - f0) * u:(x1 - f0) * u]
+        raw = clamp_prediction(raw)[:, :, (y0 - e0) * u:(y1 - e0) * u, (x0 - f0) * u:(x1 - f0) * u]
         self.shading.inverse_ao = self.model.inverse_ao
         return raw, self.shading(raw)
 

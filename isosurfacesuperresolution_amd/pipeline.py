@@ -16,7 +16,7 @@ from . import ops
 from .inference.flowfill import fill_flow
 from .models.rcan import RCAN
 from .models.tecogan import TecoGAN
-from .utils import ScreenSpaceShading
+from .utils import ScreenSpaceShading, clamp_prediction
 from .volumes import fmt3
 
 
@@ -348,11 +348,8 @@ class SuperResolutionPipeline:
             self.previous = torch.clamp(raw, 0, 1)
             return self.previous
         # mainGUI.py:594-599 -- this tensor is also next frame's "previous high-res" input
-        raw = torch.cat([torch.clamp(raw[:, 0:1], -1, +1),
-                         ScreenSpaceShading.normalize(raw[:, 1:4], dim=1),
-                         torch.clamp(raw[:, 4:], 0, 1)], dim=1)
-        self.previous = raw
-        return raw
+        self.previous = clamp_prediction(raw)
+        return self.previous
 
     def _assemble(self, gbuffer, flow, prev):
         """The network input of a frame: packed-split straight into the dataflow trunk's workspace where that launch will take it

@@ -46,9 +46,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import models
 from .inference.loadedmodel import guarded_forward
-from .utils import MSSSIM, PSNR, MeanVariance, ScreenSpaceShading, initialImage
+from .train import clip_recurrence
+from .utils import MSSSIM, PSNR, MeanVariance, ScreenSpaceShading, clamp_prediction
 
 UPSCALING = 4
 BORDER = 15
@@ -337,23 +337,19 @@ def load_models(specs, device, upscaling=UPSCALING):
     return out
 
 
+def _batch_of_one(clip):
+    """[T, ...] -> [1, T, ...] as ``train.clip_recurrence`` takes a clip (a one-frame clip may come without flow)."""
+    return clip[None] if clip is not None else None
+
+
 def run_clip(net, low, high, flow, stats, upscaling=UPSCALING):
     """One clip through one model with the recurrence of ``:326-371``; returns the clip's row."""
-    nf = low.shape[0]
-    previous_output = None
-    for j in range(nf):
-        if j == 0:
-            previous_warped = initialImage(low[0:1], 6, 'zero', False, upscaling)
-        else:
-            previous_warped = models.VideoTools.warp_upscale(previous_output, flow[j - 1:j], upscaling, special_mask=True)
-        single_input = torch.cat((low[j:j + 1], models.VideoTools.flatten_high(previous_warped, upscaling)), dim=1)
+    def forward(single_input):
         # (on the device: with the guard contract of LoadedModel.inference around the call -- poll, first-frame range check, publish;
         # run_statistics flushes the last frame's words at the end of the clip)
-        prediction = net(single_input)[0] if isinstance(net, SimpleUpsample) else guarded_forward(net, single_input)
-        prediction = torch.cat([torch.clamp(prediction[:, 0:1], -1, +1), ScreenSpaceShading.normalize(prediction[:, 1:4], dim=1),
-                                torch.clamp(prediction[:, 4:6], 0, +1)], dim=1)
-        stats.add_timestep_sample(prediction, high[j:j + 1], low[j:j + 1])
-        previous_output = prediction
+        return clamp_prediction(net(single_input)[0] if isinstance(net, SimpleUpsample) else guarded_forward(net, single_input))
+    for frame in clip_recurrence(forward, low[None], _batch_of_one(flow), 6, upscale=upscaling):
+        stats.add_timestep_sample(frame.output, high[frame.j:frame.j + 1], low[frame.j:frame.j + 1])
     return stats
 
 
@@ -416,33 +412,29 @@ COLOUR_COLUMNS = ("PSNR-color", "SSIM-color")
 COLOUR_OWN_CHANNELS = 8                 # what ShadedModel feeds: shaded RGB, mask in [0, 1], normal, depth (:156-160)
 
 
-def _clamp_prediction(prediction):
-    """mask to [-1, 1], unit normals, depth and AO to [0, 1] (``:138-140,185-187``)."""
-    return torch.cat([torch.clamp(prediction[:, 0:1], -1, +1), ScreenSpaceShading.normalize(prediction[:, 1:4], dim=1),
-                      torch.clamp(prediction[:, 4:6], 0, +1)], dim=1)
-
-
 class BaselineColourModel:
-    """``SimpleUpsample`` of ``:112-143``: the five input channels resized, AO = 1, clamped, shaded.  -> (colour, fed-back prediction)"""
+    """``SimpleUpsample`` of ``:112-143``: the five input channels resized, AO = 1, clamped (``:138-140``), shaded.  Like the other two
+    wrappers it takes a frame's input -- the five low-resolution channels, then the flattened warped previous image -- and returns
+    (colour, the image to feed back)."""
     prev_input_channels = 6
 
     def __init__(self, upscaling, upsample, shading):
         self.resize, self.shading = SimpleUpsample(upscaling, upsample), shading
 
-    def __call__(self, sample_low, previous_warped_flattened):
-        prediction = _clamp_prediction(self.resize(sample_low)[0])
+    def __call__(self, single_input):
+        prediction = clamp_prediction(self.resize(single_input)[0])
         return self.shading(prediction), prediction
 
 
 class UnshadedColourModel:
-    """``UnshadedModel`` of ``:169-190``: an unshaded network, its clamped G-buffer shaded afterwards and fed back."""
+    """``UnshadedModel`` of ``:169-190``: an unshaded network, its clamped G-buffer (``:185-187``) shaded afterwards and fed back."""
     prev_input_channels = 6
 
     def __init__(self, net, shading):
         self.net, self.shading = net, shading
 
-    def __call__(self, sample_low, previous_warped_flattened):
-        prediction = _clamp_prediction(guarded_forward(self.net, torch.cat((sample_low, previous_warped_flattened), dim=1)))
+    def __call__(self, single_input):
+        prediction = clamp_prediction(guarded_forward(self.net, single_input))
         return self.shading(prediction), prediction
 
 
@@ -454,7 +446,8 @@ class ShadedColourModel:
     def __init__(self, net, shading):
         self.net, self.shading = net, shading
 
-    def __call__(self, sample_low, previous_warped_flattened):
+    def __call__(self, single_input):
+        sample_low, previous_warped_flattened = single_input[:, 0:5], single_input[:, 5:]
         own = torch.cat([self.shading(sample_low), sample_low[:, 0:1] * 0.5 + 0.5, sample_low[:, 1:4], sample_low[:, 4:5]], dim=1)
         color = torch.clamp(guarded_forward(self.net, torch.cat((own, previous_warped_flattened), dim=1)), 0, 1)
         return color, color
@@ -555,14 +548,9 @@ def run_colour_clip(model, low, high, flow, stats, upscaling=UPSCALING):
     """One clip through one wrapper with the recurrence of ``:314-346``: the previous image (6 or 3 channels, zeros on frame 0) is
     warped with ``special_mask=True`` -- for a three-channel previous COLOUR as well, whose red channel the reference thereby treats
     as a mask; kept."""
-    previous_output = None
-    for j in range(low.shape[0]):
-        if j == 0:
-            previous_warped = initialImage(low[0:1], model.prev_input_channels, 'zero', False, upscaling)
-        else:
-            previous_warped = models.VideoTools.warp_upscale(previous_output, flow[j - 1:j], upscaling, special_mask=True)
-        pred_color, previous_output = model(low[j:j + 1], models.VideoTools.flatten_high(previous_warped, upscaling))
-        stats.add_timestep_sample(pred_color, high[j:j + 1])
+    for frame in clip_recurrence(model, low[None], _batch_of_one(flow), model.prev_input_channels, upscale=upscaling,
+                                 feedback=lambda output: output[1]):                    # a wrapper returns (colour, the image to feed back)
+        stats.add_timestep_sample(frame.output[0], high[frame.j:frame.j + 1])
     return stats
 
 

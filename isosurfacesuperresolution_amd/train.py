@@ -13,12 +13,26 @@ scheduler of ``:287-300``: Adam(lr 1e-4), ``StepLR(lrStep, 0.5)`` stepped at epo
         previous_output = cat(clamp(mask), normalize(normal), clamp(depth), clamp(ao))   # NOT detached
       loss.backward(); optimizer.step()
 
+The reference writes that frame loop out in every trainer, test pass and statistics script.  Here it stands once, as the generator
+``clip_recurrence`` (initial image, warp of the fed-back output, ``flatten_high`` + ``cat``, the forward, the upsampled inputs of the
+adversarial terms), and the fed-back image once, as ``utils.clamp_prediction``; every loop below is "for frame in clip_recurrence:
+call the criterion, accumulate":
+
+    ``clip_loss``                 the loop above (``trainNormal``, and the generator phase of the adversarial mode); may take the
+                                  fused ``ops.recurrent_input`` for feedback + warp + cat
+    ``discriminator_clip_loss``   the generator under ``no_grad``, ``criterion.train_discriminator`` per frame (``:511-566``)
+    ``evaluate``                  ``test(epoch)`` (``:639-726``): no gradients, every term of the criterion averaged
+    ``colour_clip_loss``          the colour networks (``mainVideo.py:381-434``: three output channels, starts from zeros, the clamped
+                                  prediction is what the criterion sees and what is fed back, a criterion the caller brings);
+                                  ``train_step`` and ``GraphedTrainStep`` take it as ``clip_loss=``
+    ``stats.run_clip`` / ``stats.run_colour_clip``   the two tables, a clip as a batch of one
+
 ``adversarial_step`` / ``fit_adversarial`` restate the reference's second training mode, ``trainAdv_v2`` (``:475-636``), which it
 enters as soon as ``--losses`` names an adversarial term (``:296-312``): per batch the discriminators are trained on the generator's
 frozen predictions, then the generator against the discriminators.
 
-``colour_clip_loss`` is the same loop for the colour networks (``mainVideo.py:381-434``: three output channels, the clamped
-prediction fed back, a criterion the caller brings); ``train_step`` and ``GraphedTrainStep`` take it as ``clip_loss=``.
+``GraphedTrainStep`` and ``GraphedAdversarialStep`` are those two steps captured in a HIP graph; how a step is warmed up, captured,
+put back and replayed is ``_CapturedStep``'s, once.  ``save_checkpoint`` / ``save_adversarial_checkpoint`` write through one writer.
 
 The reference has nothing distributed.  ``DataParallelTrainer`` adds the
 MI355X form: one process per GPU, the global batch split over ranks, identical initial weights
@@ -27,7 +41,8 @@ MI355X form: one process per GPU, the global batch split over ranks, identical i
 launches), averaged, then a local Adam step.  Loss terms are batch means, so averaged gradients
 equal the single-process gradients of the global batch.
 """
-import math
+import collections
+import contextlib
 import os
 import warnings
 
@@ -37,7 +52,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .models import VideoTools
-from .utils import ScreenSpaceShading, initialImage
+from .utils import clamp_prediction, initialImage
 
 
 def backward(loss):
@@ -52,59 +67,91 @@ def backward(loss):
         loss.backward()
 
 
+Frame = collections.namedtuple("Frame", "j output previous_warped_loss input_high previous_input")
+
+
+def clip_recurrence(forward, input, flow, channels, target=None, initial_image="zero", upscale=4, disable_temporal=False,
+                    special_mask=True, feedback=None, fused=False, upsample=None):
+    """The reference's clip recurrence, stated once (mainVideoUnshaded.py:413-465 and its copies in the discriminator phase, the test
+    pass, mainVideo.py:381-434 and the two statistics scripts).  input [B,T,C,h,w], flow [B,T,2,h,w]; for every frame j
+
+        j == 0 or disable_temporal:  previous_warped = initialImage(input[:,0], channels, initial_image)
+        otherwise:                   previous_warped = warp_upscale(feedback(output of frame j-1), flow[:,j-1], special_mask)
+        output = forward(cat(input[:,j], flatten_high(previous_warped)))
+
+    and yields a ``Frame`` (j, output, previous_warped_loss, input_high, previous_input) for the caller to consume.  ``output`` is whatever
+    ``forward`` returns -- the caller decides there whether the model runs under ``no_grad``, through a guard, with a clamp behind it;
+    ``feedback`` (identity unless given) makes the image that is warped into the next frame from it, NOT detached.
+    ``previous_warped_loss``: target[:,0] where a frame starts from the initial image, ``previous_warped`` elsewhere (None without a
+    ``target``).  ``upsample`` (an interpolation mode): the low-resolution inputs the reference hands to its criterion
+    (mainVideoUnshaded.py:432-452) -- ``input_high`` = input[:,j] upsampled, ``previous_input`` = input[:,j-1] upsampled and warped
+    (input[:,0] upsampled at a start); both None without it.  ``fused``: where ``ops.recurrent_input`` supports the operands, feedback
+    (it is ``clamp_prediction`` there), warp, space-to-depth and cat are ONE kernel on the raw output."""
+    size = (input.shape[3] * upscale, input.shape[4] * upscale)
+    kw = dict(mode=upsample, **({"align_corners": False} if upsample in ("bilinear", "bicubic") else {}))
+    output = input_high = previous_input = None
+    for j in range(input.shape[1]):
+        single_input = None
+        if j == 0 or disable_temporal:
+            previous_warped = initialImage(input[:, 0], channels, initial_image, False, upscale)
+            previous_warped_loss = target[:, 0] if target is not None else None
+            if upsample:
+                previous_input = F.interpolate(input[:, 0], size=size, **kw)
+        else:
+            if fused and ops.recurrent_input_supported(output, input[:, j], flow[:, j - 1], upscale):
+                single_input, previous_warped = ops.recurrent_input(output, input[:, j], flow[:, j - 1])
+            else:
+                previous_output = output if feedback is None else feedback(output)
+                previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=special_mask)
+            previous_warped_loss = previous_warped
+            if upsample:
+                previous_input = VideoTools.warp_upscale(F.interpolate(input[:, j - 1], size=size, **kw), flow[:, j - 1], upscale,
+                                                         special_mask=True)
+        if single_input is None:
+            single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
+        output = forward(single_input)
+        if upsample:
+            input_high = F.interpolate(input[:, j], size=size, **kw)
+        yield Frame(j, output, previous_warped_loss, input_high, previous_input)
+
+
+@contextlib.contextmanager
+def lazy_values(criterion):
+    """``criterion.lazy_values = True`` for the block -- the criterion returns its terms as detached tensors, no read-back -- and back to
+    what it was however the block ends.  A criterion without the attribute (the colour trainers' callables) is left alone."""
+    before = getattr(criterion, 'lazy_values', None)
+    if before is not None:
+        criterion.lazy_values = True
+    try:
+        yield
+    finally:
+        if before is not None:
+            criterion.lazy_values = before
+
+
+def _refresh_split_images(model, target):
+    if ops.TRAIN_SPLIT and not ops.TRAIN_BF16 and target.is_cuda and torch.is_grad_enabled():
+        # every weight changed in the last optimizer step: refresh all split-kernel weight images in two launches
+        ops.prepare_split_many([m.weight for m in model.modules()
+                                if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.out_channels > 8 and m.in_channels > 8])
+
+
 def clip_loss(model, criterion, input, flow, target, initial_image="zero", upscale=4, upsample="bilinear",
               disable_temporal=False, fused_recurrence=True):
     """input [B,T,5,h,w], flow [B,T,2,h,w], target [B,T,6,4h,4w] -> (loss tensor, sum of the per-frame losses).
     The reference reads every frame's loss back with ``.item()`` (mainVideoUnshaded.py:454); here the sum is accumulated
     on the device and read back ONCE after the last frame, so the whole clip is enqueued without a stall."""
-    B, T, Cout, Hh, Wh = target.shape
-    if ops.TRAIN_SPLIT and not ops.TRAIN_BF16 and target.is_cuda and torch.is_grad_enabled():
-        # every weight changed in the last optimizer step: refresh all split-kernel weight images in two launches
-        ops.prepare_split_many([m.weight for m in model.modules()
-                                if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.out_channels > 8 and m.in_channels > 8])
-    prediction = None
-    loss = 0
-    loss_sum = None
-    lazy_before = getattr(criterion, 'lazy_values', None)
-    if lazy_before is not None:
-        criterion.lazy_values = True
-    kw = dict(mode=upsample, **({"align_corners": False} if upsample in ("bilinear", "bicubic") else {}))
-    # the reference upsamples (and warps) the low-resolution inputs for every frame and hands them to the criterion
-    # (mainVideoUnshaded.py:432-452); only LossNetUnshaded's adversarial terms read them, so a criterion without a
-    # discriminator says so (uses_input = False) and is not fed
+    _refresh_split_images(model, target)
+    # only LossNetUnshaded's adversarial terms read the upsampled inputs, so a criterion without a discriminator says so
+    # (uses_input = False) and is not fed
     feed_inputs = getattr(criterion, 'uses_input', True)
-    previous_input = input_high = None
-    for j in range(T):
-        if j == 0 or disable_temporal:
-            previous_warped = initialImage(input[:, 0], Cout, initial_image, False, upscale)
-            previous_warped_loss = target[:, 0]
-            if feed_inputs:
-                previous_input = F.interpolate(input[:, 0], size=(Hh, Wh), **kw)
-            single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
-        else:
-            if fused_recurrence and ops.recurrent_input_supported(prediction, input[:, j], flow[:, j - 1], upscale):
-                # clamp / normalize of the previous prediction, warp, space-to-depth and cat in one kernel
-                single_input, previous_warped = ops.recurrent_input(prediction, input[:, j], flow[:, j - 1])
-            else:
-                previous_output = torch.cat([
-                    torch.clamp(prediction[:, 0:1], -1, +1),
-                    ScreenSpaceShading.normalize(prediction[:, 1:4], dim=1),
-                    torch.clamp(prediction[:, 4:5], 0, +1),
-                    torch.clamp(prediction[:, 5:6], 0, +1)], dim=1)       # NOT detached: gradients flow through time
-                previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=True)
-                single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
-            previous_warped_loss = previous_warped
-            if feed_inputs:
-                previous_input = F.interpolate(input[:, j - 1], size=(Hh, Wh), **kw)
-                previous_input = VideoTools.warp_upscale(previous_input, flow[:, j - 1], upscale, special_mask=True)
-        prediction, _ = model(single_input)
-        if feed_inputs:
-            input_high = F.interpolate(input[:, j], size=(Hh, Wh), **kw)
-        loss0, _ = criterion(target[:, j], prediction, input_high, previous_input, previous_warped_loss)
-        loss = loss + loss0
-        loss_sum = loss0.detach() if loss_sum is None else loss_sum + loss0.detach()
-    if lazy_before is not None:
-        criterion.lazy_values = lazy_before
+    loss, loss_sum = 0, None
+    with lazy_values(criterion):
+        for f in clip_recurrence(lambda x: model(x)[0], input, flow, target.shape[2], target, initial_image, upscale, disable_temporal,
+                                 feedback=clamp_prediction, fused=fused_recurrence, upsample=upsample if feed_inputs else None):
+            loss0, _ = criterion(target[:, f.j], f.output, f.input_high, f.previous_input, f.previous_warped_loss)
+            loss = loss + loss0
+            loss_sum = loss0.detach() if loss_sum is None else loss_sum + loss0.detach()
     return loss, loss_sum
 
 
@@ -122,28 +169,13 @@ def colour_clip_loss(model, criterion, input, flow, target, upscale=4, disable_t
     ``criterion``: any callable with the signature of the reference's ``LossNet.forward`` -> (loss, values).  The reference's own
     call of it is commented out in favour of two hard-wired MSE terms (:424-430), and ``losses.LossNet`` (VGG and GAN terms) is not
     part of this package: the caller brings the criterion."""
-    B, T, Cout, Hh, Wh = target.shape
-    if ops.TRAIN_SPLIT and not ops.TRAIN_BF16 and target.is_cuda and torch.is_grad_enabled():
-        # every weight changed in the last optimizer step: refresh all split-kernel weight images in two launches
-        ops.prepare_split_many([m.weight for m in model.modules()
-                                if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.out_channels > 8 and m.in_channels > 8])
-    previous_output = None
-    loss = 0
-    loss_sum = None
-    for j in range(T):
-        if j == 0 or disable_temporal:
-            previous_warped = torch.zeros(B, Cout, Hh, Wh, dtype=input.dtype, device=input.device)
-            previous_warped_loss = target[:, 0]
-        else:
-            previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=False)
-            previous_warped_loss = previous_warped
-        single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
-        prediction, _ = model(single_input)
-        prediction = torch.clamp(prediction, 0, 1)
-        loss0, _ = criterion(target[:, j], prediction, input[:, j], previous_warped_loss)
+    _refresh_split_images(model, target)
+    loss, loss_sum = 0, None
+    for f in clip_recurrence(lambda x: torch.clamp(model(x)[0], 0, 1), input, flow, target.shape[2], target, "zero", upscale,
+                             disable_temporal, special_mask=False):
+        loss0, _ = criterion(target[:, f.j], f.output, input[:, f.j], f.previous_warped_loss)
         loss = loss + loss0
         loss_sum = loss0.detach() if loss_sum is None else loss_sum + loss0.detach()
-        previous_output = prediction
     return loss, loss_sum
 
 
@@ -329,37 +361,15 @@ def discriminator_clip_loss(model, criterion, input, flow, target, initial_image
     """The discriminator phase's loop over the frames of a clip (mainVideoUnshaded.py:511-566): the generator runs without gradients,
     ``criterion.train_discriminator`` compares each frame's prediction with the ground truth -> (loss tensor, sum of the gt scores, sum
     of the pred scores; device tensors, nothing is read back)."""
-    B, T, Cout, Hh, Wh = target.shape
-    kw = dict(mode=upsample, **({"align_corners": False} if upsample in ("bilinear", "bicubic") else {}))
-    lazy_before = criterion.lazy_values
-    criterion.lazy_values = True
-    loss, gt_sum, pred_sum, previous_output = 0, 0, 0, None
-    try:
-        for j in range(T):
-            if j == 0 or disable_temporal:
-                previous_warped = initialImage(input[:, 0], Cout, initial_image, False, upscale)
-                previous_warped_loss = target[:, 0]
-                previous_input = F.interpolate(input[:, 0], size=(Hh, Wh), **kw)
-            else:
-                previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=True)
-                previous_warped_loss = previous_warped
-                previous_input = VideoTools.warp_upscale(F.interpolate(input[:, j - 1], size=(Hh, Wh), **kw), flow[:, j - 1], upscale,
-                                                         special_mask=True)
-            single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
-            with torch.no_grad():
-                prediction, _ = model(single_input)
+    loss, gt_sum, pred_sum = 0, 0, 0
+    with lazy_values(criterion):
+        for f in clip_recurrence(torch.no_grad()(lambda x: model(x)[0]), input, flow, target.shape[2], target, initial_image, upscale,
+                                 disable_temporal, feedback=clamp_prediction, upsample=upsample):
             # at j = 0 this is frame -1 of the clip, the LAST one, warped by flow[:, -1] (mainVideoUnshaded.py:543-547 index with j - 1)
-            gt_prev_warped = VideoTools.warp_upscale(target[:, j - 1], flow[:, j - 1], upscale, special_mask=True)
-            input_high = F.interpolate(input[:, j], size=(Hh, Wh), **kw)
-            loss0, gt_score, pred_score = criterion.train_discriminator(input_high, target[:, j], previous_input, gt_prev_warped,
-                                                                        prediction, previous_warped_loss)
+            gt_prev_warped = VideoTools.warp_upscale(target[:, f.j - 1], flow[:, f.j - 1], upscale, special_mask=True)
+            loss0, gt_score, pred_score = criterion.train_discriminator(f.input_high, target[:, f.j], f.previous_input, gt_prev_warped,
+                                                                        f.output, f.previous_warped_loss)
             loss, gt_sum, pred_sum = loss + loss0, gt_sum + gt_score, pred_sum + pred_score
-            previous_output = torch.cat([torch.clamp(prediction[:, 0:1], -1, +1),
-                                         ScreenSpaceShading.normalize(prediction[:, 1:4], dim=1),
-                                         torch.clamp(prediction[:, 4:5], 0, +1),
-                                         torch.clamp(prediction[:, 5:6], 0, +1)], dim=1)
-    finally:
-        criterion.lazy_values = lazy_before
     return loss, gt_sum, pred_sum
 
 
@@ -416,14 +426,9 @@ def save_adversarial_checkpoint(modeldir, epoch, model, parameters, criterion, g
     'parameters', the two optimizer and the two scheduler objects, and each discriminator's ``state_dict`` under its attribute name --
     ``--pretrainedDiscr`` and the reference's restore read ``checkpoint['discriminator']`` (:326, :367).  The whole criterion object of
     :809 is NOT written: the reference never reads it back, and it would need new names in the restricted unpickler."""
-    os.makedirs(modeldir, exist_ok=True)
-    path = checkpoint_path(modeldir, epoch)
-    opt_dict = dict(parameters) if isinstance(parameters, dict) else dict(vars(parameters))
-    state = {'epoch': epoch + 1, 'model': model, 'parameters': opt_dict, 'gen_optimizer': gen_optimizer, 'discr_optimizer': discr_optimizer,
-             'gen_scheduler': gen_scheduler, 'discr_scheduler': discr_scheduler}
-    state.update({name: d.state_dict() for name, d in criterion.discriminators().items()})
-    torch.save(state, path)
-    return path
+    return _write_checkpoint(modeldir, epoch, model, parameters, gen_optimizer=gen_optimizer, discr_optimizer=discr_optimizer,
+                             gen_scheduler=gen_scheduler, discr_scheduler=discr_scheduler,
+                             **{name: d.state_dict() for name, d in criterion.discriminators().items()})
 
 
 def fit_adversarial(model, criterion, train_loader, test_loader, modeldir, n_epochs, parameters, device=None, lr=1e-4, lr_step=500,
@@ -511,7 +516,54 @@ def _restore_training_state(model, optimizer, snapshot):
             v.zero_()
 
 
-class GraphedTrainStep:
+class _CapturedStep:
+    """The recipe of a training step captured ONCE in a HIP graph and replayed; a subclass brings ``_eager()`` -- the step on
+    ``self.static``, returning device tensors -- and ``zero_grad()``.
+
+    ``_capture``: static batch buffers; ``warmup`` REAL steps on the example batch on a side stream (PyTorch's capture recipe: they
+    create the optimizers' state tensors and every cached buffer the capture must find in place); the capture; then every
+    (module, optimizer) pair put back to where it was -- in place, the graph holds these very tensors -- because the reference takes one
+    step per batch (mainVideoUnshaded.py:397-473).  Before the capture every cached kernel-layout weight image is declared stale: an
+    image found valid there -- after an eager forward of the same model with no step since, or of weights that the step's first phase
+    leaves alone -- would be taken from the cache with no refresh recorded, and every replay would read that old image.  Stale, each
+    weight's first use records its refresh, so the graph rebuilds its own image buffers at the start of every replay.
+
+    A replay changes the weights WITHOUT advancing ``Parameter._version`` (the captured optimizer kernels write the parameters'
+    memory directly), so every replay declares the cached images stale again (``ops.invalidate_weight_images``): inference or an
+    eager step after a replay re-prepares them from the current weights."""
+
+    def _capture(self, example_batch, pairs, warmup):
+        self.static = tuple(torch.empty_like(t) for t in example_batch)
+        for dst, src in zip(self.static, example_batch):
+            dst.copy_(src)
+        before = [_snapshot_training_state(module, optimizer) for module, optimizer in pairs] if warmup > 0 else None
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._eager()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        self.zero_grad()
+        ops.invalidate_weight_images()
+        with ops.graph_capture(self.graph):
+            captured = self._eager()
+        if before is not None:
+            for (module, optimizer), snapshot in zip(pairs, before):
+                _restore_training_state(module, optimizer, snapshot)
+        self.zero_grad()
+        ops.invalidate_weight_images()
+        return captured
+
+    def _replay(self, batch):
+        for dst, src in zip(self.static, batch):
+            dst.copy_(src, non_blocking=True)
+        self.graph.replay()
+        ops.invalidate_weight_images()
+
+
+class GraphedTrainStep(_CapturedStep):
     """The whole optimisation step (T frames forward with the recurrence, backward through time, Adam) captured ONCE in
     a HIP graph and replayed: at the per-GPU batch of BASELINE config #3 (2 clips) a step is ~1500 small launches and the
     eager loop is bound by Python, not by the GPU.  Needs a GPU, fixed batch shapes, an optimizer created with
@@ -519,12 +571,7 @@ class GraphedTrainStep:
     returned as a device tensor.  ``all_reduce`` (optional callable) runs between backward and the optimizer step --
     ``DataParallelTrainer`` passes its flat-bucket RCCL all-reduce, which is captured with the rest.  ``zero_grad``
     (optional callable) replaces ``optimizer.zero_grad(set_to_none=True)`` -- the data-parallel trainer's gradients are
-    views of its flat bucket and must stay those tensors.
-
-    A replay changes the weights WITHOUT advancing ``Parameter._version`` (the captured optimizer kernels write the
-    parameters' memory directly), so every replay declares the cached kernel-layout weight images stale
-    (``ops.invalidate_weight_images``): inference or an eager step after a replay re-prepares them from the current
-    weights.  The graph itself is unaffected: it refreshes its own image buffers at the start of every replay."""
+    views of its flat bucket and must stay those tensors."""
 
     def __init__(self, model, criterion, optimizer, example_batch, all_reduce=None, zero_grad=None, warmup=3, clip_loss=None, **kw):
         self.model, self.criterion, self.optimizer, self.kw = model, criterion, optimizer, kw
@@ -533,29 +580,7 @@ class GraphedTrainStep:
         if zero_grad is None:
             zero_grad = self.optimizer.zero_grad if isinstance(self.optimizer, FlatAdam) else (lambda: self.optimizer.zero_grad(set_to_none=True))
         self.zero_grad = zero_grad
-        self.static = tuple(torch.empty_like(t) for t in example_batch)
-        for dst, src in zip(self.static, example_batch):
-            dst.copy_(src)
-        # The warm-up steps are REAL optimisation steps on the example batch (they create the optimizer's state tensors and
-        # every cached buffer the capture must find in place); the reference takes one step per batch (trainNormal,
-        # mainVideoUnshaded.py:397-473), so model and optimizer are put back to where they were -- in place, the graph
-        # holds these very tensors -- before the first replay.
-        before = _snapshot_training_state(model, optimizer) if warmup > 0 else None
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                      # PyTorch's capture recipe: warm up on a side stream
-            for _ in range(warmup):
-                self._eager()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        self.zero_grad()
-        with ops.graph_capture(self.graph):
-            self.loss = self._eager()
-        if before is not None:
-            _restore_training_state(model, optimizer, before)
-            self.zero_grad()
-        ops.invalidate_weight_images()
+        self.loss = self._capture(example_batch, [(model, optimizer)], warmup)
 
     def _eager(self):
         input, flow, target = self.static
@@ -568,18 +593,14 @@ class GraphedTrainStep:
         return loss_sum / target.shape[1]
 
     def __call__(self, batch):
-        for dst, src in zip(self.static, batch):
-            dst.copy_(src, non_blocking=True)
-        self.graph.replay()
-        ops.invalidate_weight_images()
+        self._replay(batch)
         return self.loss
 
 
-class GraphedAdversarialStep:
+class GraphedAdversarialStep(_CapturedStep):
     """``adversarial_step`` (``disc_steps`` discriminator steps, then ``disc_steps`` generator steps with the discriminators switched to
-    ``requires_grad_(False)``) captured ONCE in one HIP graph on one stream and replayed, in the manner of ``GraphedTrainStep``: static
-    batch buffers, ``warmup`` real steps on the example batch that are undone in place -- the model, every discriminator and both
-    optimizers are back where they were before the first replay -- and ``ops.invalidate_weight_images()`` after every replay.
+    ``requires_grad_(False)``) captured ONCE in one HIP graph on one stream and replayed, as ``GraphedTrainStep``: the warm-up steps are
+    undone in place -- the model, every discriminator and both optimizers are back where they were before the first replay.
 
     ``__call__(batch)`` -> (discr_loss, gen_loss, gt_score, pred_score) as device tensors that the next replay overwrites; nothing is
     read back.  The optimizers must be ones a capture can record: Adam built with ``capturable=True``
@@ -596,34 +617,10 @@ class GraphedAdversarialStep:
                                  "(make_adversarial_optimizers(..., capturable=True))" % name)
         self.model, self.criterion, self.gen_optimizer, self.discr_optimizer = model, criterion, gen_optimizer, discr_optimizer
         self.disc_steps, self.kw = disc_steps, kw
-        self.static = tuple(torch.empty_like(t) for t in example_batch)
-        for dst, src in zip(self.static, example_batch):
-            dst.copy_(src)
         # (the criterion's state_dict is its discriminators': the loss modules and the shader hold no parameters or buffers)
-        before = ((_snapshot_training_state(model, gen_optimizer), _snapshot_training_state(criterion, discr_optimizer))
-                  if warmup > 0 else None)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._eager()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        self._zero_grad()
-        # The step's FIRST use of the discriminators' weights follows a generator phase that left them alone: their kernel-layout images
-        # would be taken from the cache and no refresh would be recorded, so that the first replay -- on the weights put back below --
-        # would read the warm-up's.  With every image declared stale the capture records a refresh at each weight's first use.
-        ops.invalidate_weight_images()
-        with ops.graph_capture(self.graph):
-            self.results = self._eager()
-        if before is not None:
-            _restore_training_state(model, gen_optimizer, before[0])
-            _restore_training_state(criterion, discr_optimizer, before[1])
-        self._zero_grad()
-        ops.invalidate_weight_images()
+        self.results = self._capture(example_batch, [(model, gen_optimizer), (criterion, discr_optimizer)], warmup)
 
-    def _zero_grad(self):
+    def zero_grad(self):
         self.gen_optimizer.zero_grad(set_to_none=True)
         self.discr_optimizer.zero_grad(set_to_none=True)
 
@@ -632,10 +629,7 @@ class GraphedAdversarialStep:
                                          **self.kw)
 
     def __call__(self, batch):
-        for dst, src in zip(self.static, batch):
-            dst.copy_(src, non_blocking=True)
-        self.graph.replay()
-        ops.invalidate_weight_images()
+        self._replay(batch)
         return self.results
 
 
@@ -727,51 +721,25 @@ def evaluate(model, criterion, loader, device, initial_image="zero", upscale=4, 
     back with ``.item()``; here everything is accumulated on the device and read once."""
     was_training = model.training
     model.eval()
-    lazy_before = getattr(criterion, 'lazy_values', None)
-    if lazy_before is not None:
-        criterion.lazy_values = True
     feed_inputs = getattr(criterion, 'uses_input', True)
-    kw = dict(mode=upsample, **({"align_corners": False} if upsample in ("bilinear", "bicubic") else {}))
     sums, frames = {}, 0
 
     def add(key, value):
         value = value.detach().double() if torch.is_tensor(value) else torch.tensor(float(value), dtype=torch.float64, device=device)
         sums[key] = value if key not in sums else sums[key] + value
-    with torch.no_grad():
+    with torch.no_grad(), lazy_values(criterion):
         for batch in loader:
             input, flow, target = (t.to(device) for t in batch)
-            B, T, Cout, Hh, Wh = target.shape
-            previous_output = previous_input = input_high = None
-            for j in range(T):
-                if j == 0 or disable_temporal:
-                    previous_warped = initialImage(input[:, 0], Cout, initial_image, False, upscale)
-                    previous_warped_loss = target[:, 0]
-                    if feed_inputs:
-                        previous_input = F.interpolate(input[:, 0], size=(Hh, Wh), **kw)
-                else:
-                    previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=True)
-                    previous_warped_loss = previous_warped
-                    if feed_inputs:
-                        previous_input = VideoTools.warp_upscale(F.interpolate(input[:, j - 1], size=(Hh, Wh), **kw),
-                                                                 flow[:, j - 1], upscale, special_mask=True)
-                single_input = torch.cat((input[:, j], VideoTools.flatten_high(previous_warped, upscale)), dim=1)
-                prediction, _ = model(single_input)
-                if feed_inputs:
-                    input_high = F.interpolate(input[:, j], size=(Hh, Wh), **kw)
-                loss0, values = criterion(target[:, j], prediction, input_high, previous_input, previous_warped_loss)
+            for f in clip_recurrence(lambda x: model(x)[0], input, flow, target.shape[2], target, initial_image, upscale, disable_temporal,
+                                     feedback=clamp_prediction, upsample=upsample if feed_inputs else None):
+                loss0, values = criterion(target[:, f.j], f.output, f.input_high, f.previous_input, f.previous_warped_loss)
                 add('total_loss', loss0)
                 mse = values[('mse', 'color')]
                 mse = mse.detach().double() if torch.is_tensor(mse) else torch.tensor(float(mse), dtype=torch.float64, device=device)
                 add('psnr', 10.0 * torch.log10(1.0 / torch.clamp(mse, min=1e-10)))
                 for key, value in values.items():
                     add(str(key), value)
-                previous_output = torch.cat([torch.clamp(prediction[:, 0:1], -1, +1),
-                                             ScreenSpaceShading.normalize(prediction[:, 1:4], dim=1),
-                                             torch.clamp(prediction[:, 4:5], 0, +1),
-                                             torch.clamp(prediction[:, 5:6], 0, +1)], dim=1)
                 frames += 1
-    if lazy_before is not None:
-        criterion.lazy_values = lazy_before
     model.train(was_training)
     if not frames:
         return {}
@@ -784,15 +752,19 @@ def checkpoint_path(modeldir, epoch):
     return os.path.join(modeldir, "model_epoch_{}.pth".format(epoch))
 
 
-def save_checkpoint(modeldir, epoch, model, parameters, optimizer, scheduler):
-    """``checkpoint(epoch)`` of mainVideoUnshaded.py:799-811: the WHOLE model, optimizer and scheduler objects plus the
-    option dict, keyed as ``inference.LoadedModel`` (and the reference's restore) read them."""
+def _write_checkpoint(modeldir, epoch, model, parameters, **entries):
+    """``model_epoch_<epoch>.pth``: 'epoch' (the next one), the WHOLE model object, the option dict and the trainer's ``entries``."""
     os.makedirs(modeldir, exist_ok=True)
     path = checkpoint_path(modeldir, epoch)
     opt_dict = dict(parameters) if isinstance(parameters, dict) else dict(vars(parameters))      # `opt_dict = vars(opt)`, :167
-    state = {'epoch': epoch + 1, 'model': model, 'parameters': opt_dict, 'optimizer': optimizer, 'scheduler': scheduler}
-    torch.save(state, path)
+    torch.save({'epoch': epoch + 1, 'model': model, 'parameters': opt_dict, **entries}, path)
     return path
+
+
+def save_checkpoint(modeldir, epoch, model, parameters, optimizer, scheduler):
+    """``checkpoint(epoch)`` of mainVideoUnshaded.py:799-811: the WHOLE model, optimizer and scheduler objects plus the
+    option dict, keyed as ``inference.LoadedModel`` (and the reference's restore) read them."""
+    return _write_checkpoint(modeldir, epoch, model, parameters, optimizer=optimizer, scheduler=scheduler)
 
 
 def find_restore_epoch(modeldir, restore_epoch=-1):

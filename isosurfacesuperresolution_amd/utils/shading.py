@@ -134,3 +134,11 @@ class ScreenSpaceShading(nn.Module):
         """``x / max(||x||, 1e-7)`` along ``dim`` (``shading.py:194-207``)."""
         eps = torch.full((1,), 1e-7, dtype=input.dtype, device=input.device)
         return input / torch.max(torch.norm(input, dim=dim, keepdim=True), eps)
+
+
+def clamp_prediction(prediction):
+    """An unshaded network's raw output [B, 6, H, W] as it is displayed, measured and fed back to the next frame: mask to [-1, 1], unit
+    normal, depth and AO to [0, 1] (``mainVideoUnshaded.py:460-465``, ``mainGUI.py:594-599``, ``mainPSNR3_AllStats.py:352-355``,
+    ``mainPSNR4_ColoredNets.py:138-140,185-187``)."""
+    return torch.cat([torch.clamp(prediction[:, 0:1], -1, +1), ScreenSpaceShading.normalize(prediction[:, 1:4], dim=1),
+                      torch.clamp(prediction[:, 4:6], 0, +1)], dim=1)

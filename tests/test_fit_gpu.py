@@ -194,6 +194,43 @@ def test_flat_adam_matches_torch_adam_on_the_network():
     assert (a - b).abs().max().item() <= 1e-6
 
 
+def test_a_step_captured_after_an_eager_forward_refreshes_every_weight_image():
+    """``GraphedTrainStep(warmup=0)`` on a model that has just run a forward (an ``evaluate`` before training starts): every kernel-layout
+    weight image is cached and valid when the capture begins.  A capture that took them from the cache would record no refresh, and every
+    replay after the first would read the images of the initial weights.  Three replays against the eager ``train_step`` sequence of a
+    twin from the same seed, the network and batch of ``test_flat_adam_matches_torch_adam_on_the_network`` at lr 1e-3 (losses 3.70,
+    34.57, 7.93).
+
+    Bound (profiles/train_loops_refactor.md): WITHOUT the forward before it, the same graph at the parent commit differs from the eager
+    sequence by at most 2.38e-4 of the loss (0, 2.2e-7 and 2.38e-4 at the three steps, six runs; two eager runs differ by as much -- the
+    warp's backward adds with float atomics, so the weights of the third step move from run to run); four times that is allowed.  With
+    stale images -- the parent commit, this test -- the second and third loss are 31.49 and 4.38: 8.9e-2 and 4.5e-1 away."""
+    from isosurfacesuperresolution_amd import losses, models, train
+    g = torch.Generator().manual_seed(2)
+    inp = torch.rand(2, 2, 5, 32, 32, generator=g); inp[:, :, 0] = inp[:, :, 0] * 2 - 1
+    flow = (torch.rand(2, 2, 2, 32, 32, generator=g) - 0.5) * 0.05
+    tgt = torch.rand(2, 2, 6, 128, 128, generator=g); tgt[:, :, 0] = tgt[:, :, 0] * 2 - 1
+    batch = tuple(t.cuda() for t in (inp, flow, tgt))
+    hist = {}
+    for kind in ("eager", "graph"):
+        torch.manual_seed(124)
+        net = models.createNetwork('EnhanceNet', 4, 101, [0, 1, 2, 3, 4], 6, OPT).cuda()
+        crit = losses.LossNetUnshaded('cuda', 5, 6, 128, 16, OPT).cuda()
+        optim, _ = train.make_optimizer(net, lr=1e-3, capturable=True, tensor_lr=True, flat=True)
+        if kind == "eager":
+            hist[kind] = [train.train_step(net, crit, optim, batch, initial_image="zero") for _ in range(3)]
+            continue
+        net.eval()
+        with torch.no_grad():
+            net(torch.cat((batch[0][:, 0], torch.zeros(2, 96, 32, 32, device="cuda")), dim=1))       # frame 0's input
+        net.train()
+        step = train.GraphedTrainStep(net, crit, optim, batch, warmup=0, initial_image="zero")
+        hist[kind] = [float(step(batch)) for _ in range(3)]
+    rel = [abs(a - b) / abs(b) for a, b in zip(hist["graph"], hist["eager"])]
+    print("eager", hist["eager"], "graph", hist["graph"], "relative difference", rel)
+    assert max(rel) <= 4 * 2.38e-4, (hist, rel)
+
+
 @pytest.mark.keep_garbage
 def test_capture_survives_uncollected_gpu_garbage():
     """Round 3's abort (``Fatal Python error: Aborted``, main thread ``Garbage-collecting`` inside ``GraphedTrainStep.__init__``): a
