@@ -704,6 +704,28 @@ int isrBatchNormGradSums(const float* dy, const float* x, const float* y, const 
 int isrBatchNormBackward(const float* dy, const float* x, const float* y, const float* mean, const float* invstd, const float* gamma,
                          const float* coef, float* dx, int N, int C, int H, int W, void* stream);
 
+/* Training batches from device-resident clips (csrc/sr_dataset.hip; dataset_video.DeviceClips).  ONE launch on `stream` writes the three
+ * packed fp32 tensors of a batch: input [B][T][Cl][c][c], flowOut [B][T][2][c][c], target [B][T][Ch][r c][r c] -- what
+ * DatasetFromSamples.__getitem__, data_augmentation and the default collate produce on the host, bit for bit (a value is copied, or
+ * copied with its sign bit flipped).
+ *   high, low, flow : flat fp32 device buffers holding every clip, [T][Ch][r H][r W], [T][Cl][H][W] and [T][2][H][W], one after the other
+ *   clipTable       : device int64 [clips][5]: element offset of the clip in high, in low and in flow, low-resolution height H, width W
+ *   sampleTable     : device int32 [numSamples][4]: clip, first row x0 and first column y0 of the low-resolution crop
+ *                     [x0, x0 + c) x [y0, y0 + c) (the high-resolution one is r times that), augmentation mode 0..3
+ *   indices         : device int64 [B]: the samples of the batch.  The kernel clamps each to [0, numSamples - 1]; the tables are the
+ *                     caller's responsibility (offsets inside the buffers, boxes inside their clips).
+ *   augment         : 0: no flips.  Otherwise mode bit 0 reverses the rows of all three crops and negates the channels whose bit is set
+ *                     in lowNegX / flowNegX, bit 1 reverses the columns and negates the channels of lowNegY / flowNegY.
+ *   highQuadAligned : the caller's word that every high offset of clipTable is a multiple of four elements.  With it, r a multiple of
+ *                     four and 16-byte aligned `high` and `target`, the high-resolution part moves 16 bytes per lane.
+ * All addressing is in 64-bit element offsets.  B <= 65535, Cl and Ch <= 32, fewer than 2^31 values per batch element and tensor
+ * (isrClipGatherSupported says so beforehand: anything else returns -3).  No host synchronisation: the launch can be captured. */
+int isrClipGatherSupported(int B, int T, int Cl, int Ch, int c, int r);
+int isrClipGather(const float* high, const float* low, const float* flow, const long long* clipTable, const int* sampleTable,
+                  long long numSamples, const long long* indices, int B, int T, int Cl, int Ch, int c, int r, int augment,
+                  unsigned lowNegX, unsigned lowNegY, unsigned flowNegX, unsigned flowNegY, int highQuadAligned,
+                  float* input, float* flowOut, float* target, void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

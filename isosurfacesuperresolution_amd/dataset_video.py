@@ -11,6 +11,9 @@ Restates the array branch of ``SuperresolutionNetwork/datasetVideo.py`` (``colle
 * samples are sorted by clip index and the LAST ``test_fraction`` of them form the test set
   (``:300-301,328-334``) so that train and test never share a clip region ordering;
 * optional flip augmentation with the sign fix-ups of ``:31-78`` (off by default as in the reference).
+
+``DatasetFromSamples`` under a ``DataLoader`` is the reference's host path.  ``DeviceClips`` + ``DeviceBatchLoader`` keep the clips
+on the device and make a batch one gather launch (``ops.gather_clips``), with the same split, order and bits.
 """
 import os
 import random
@@ -110,6 +113,120 @@ class DatasetFromSamples(data.Dataset):
         low, high, flow = data_augmentation(low, high, flow, s.augmentation, self.augmentation)
         return (torch.from_numpy(np.ascontiguousarray(low)), torch.from_numpy(np.ascontiguousarray(flow)),
                 torch.from_numpy(np.ascontiguousarray(high)))
+
+
+class DeviceClips:
+    """A ``DatasetData`` resident on ``device``: every clip uploaded ONCE, clip by clip, into three flat fp32 buffers (``high``, ``low``,
+    ``flow``), plus the two tables ``ops.gather_clips`` reads -- ``table`` int64 [clips, 5] (element offset of the clip in each buffer,
+    low-resolution height and width; clips may differ in size) and ``samples`` int32 [n, 4] (clip, first row, first column of the
+    low-resolution crop, augmentation mode), in the order of ``dataset_data.samples``.  A batch is then one launch
+    (``DeviceBatchLoader``).  Everything the kernel relies on is checked here, on the host: a clip that is not fp32 and a sample whose
+    box leaves its clip raise ``ValueError``; a set that does not fit in the device's free memory is refused with the byte counts.
+    ``device="cpu"`` holds CPU tensors: the same objects run everywhere.  ``nbytes``: what the buffers and tables take."""
+
+    def __init__(self, dataset_data, device="cuda"):
+        dd = dataset_data
+        self.device = torch.device(device)
+        if not dd.images_low:
+            raise ValueError("DeviceClips: no clips")
+        self.frames, self.low_channels = int(dd.images_low[0].shape[0]), int(dd.images_low[0].shape[1])
+        self.high_channels = int(dd.images_high[0].shape[1])
+        self.crop = int(dd.crop_size)
+        self.upscale = int(dd.images_high[0].shape[2]) // int(dd.images_low[0].shape[2])
+        T, Cl, Ch, r, c = self.frames, self.low_channels, self.high_channels, self.upscale, self.crop
+        rows, off = [], [0, 0, 0]
+        for i, (high, low, flow) in enumerate(zip(dd.images_high, dd.images_low, dd.flow_low)):
+            for name, a in (("high", high), ("low", low), ("flow", flow)):
+                if a.dtype != np.float32:
+                    raise ValueError("DeviceClips: clip %d: %s is %s, not float32" % (i, name, a.dtype))
+            H, W = int(low.shape[2]), int(low.shape[3])
+            if low.shape != (T, Cl, H, W) or flow.shape != (T, 2, H, W) or high.shape != (T, Ch, r * H, r * W) or r < 1:
+                raise ValueError("DeviceClips: clip %d: shapes high %s, low %s, flow %s are not [%d, %d, %d H, %d W], [%d, %d, H, W], [%d, 2, H, W]"
+                                 % (i, high.shape, low.shape, flow.shape, T, Ch, r, r, T, Cl, T))
+            rows.append((off[0], off[1], off[2], H, W))
+            off[0] += -(-high.size // 4) * 4              # every clip starts on a multiple of four elements: 16-byte rows for the gather
+            off[1] += low.size
+            off[2] += flow.size
+        table = []
+        for j, s in enumerate(dd.samples):
+            x0, x1, y0, y1 = (int(v) for v in s.crop_low)
+            if not 0 <= s.index < len(rows):
+                raise ValueError("DeviceClips: sample %d: clip %d of %d" % (j, s.index, len(rows)))
+            H, W = rows[s.index][3:]
+            if x1 - x0 != c or y1 - y0 != c or x0 < 0 or y0 < 0 or x1 > H or y1 > W:
+                raise ValueError("DeviceClips: sample %d: the crop rows %d:%d, columns %d:%d is not a %d x %d box inside clip %d (%d x %d)"
+                                 % (j, x0, x1, y0, y1, c, c, s.index, H, W))
+            if tuple(int(v) for v in s.crop_high) != (r * x0, r * x1, r * y0, r * y1):
+                raise ValueError("DeviceClips: sample %d: the high-resolution box %s is not %d times the low-resolution one" % (j, tuple(s.crop_high), r))
+            if not 0 <= int(s.augmentation) < MAX_AUGMENTATION_MODE:
+                raise ValueError("DeviceClips: sample %d: augmentation mode %d" % (j, s.augmentation))
+            table.append((s.index, x0, y0, int(s.augmentation)))
+        if not table:
+            raise ValueError("DeviceClips: no samples")
+        self.nbytes = 4 * sum(off) + 8 * 5 * len(rows) + 4 * 4 * len(table)
+        if self.device.type == "cuda":
+            free, total = torch.cuda.mem_get_info(self.device)
+            if self.nbytes > free:
+                raise RuntimeError("DeviceClips: the clips take %d bytes (high %d, low %d, flow %d); %s has %d of %d bytes free"
+                                   % (self.nbytes, 4 * off[0], 4 * off[1], 4 * off[2], self.device, free, total))
+        self.high, self.low, self.flow = (torch.empty(n, dtype=torch.float32, device=self.device) for n in off)
+        for row, arrays in zip(rows, zip(dd.images_high, dd.images_low, dd.flow_low)):
+            for buf, start, a in zip((self.high, self.low, self.flow), row, arrays):
+                buf[start:start + a.size].copy_(torch.from_numpy(np.ascontiguousarray(a)).reshape(-1))
+        self.high_quad_aligned = True
+        self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)
+        self.samples = torch.tensor(table, dtype=torch.int32).to(self.device)
+        self.num_samples, self.num_clips = len(table), len(rows)
+
+
+class DeviceBatchLoader:
+    """The training loops' fast path: an iterable (with ``__len__``) of ``(input, flow, target)`` batches on the device, each ONE launch
+    of ``ops.gather_clips`` on a ``DeviceClips`` (a ``DatasetData`` is uploaded first) -- what ``DataLoader(DatasetFromSamples(...))``
+    yields, bit for bit, without the host's slicing, collating and copying.
+
+    Split: ``DatasetFromSamples``' -- the samples are sorted by clip and the last ``int(n * test_fraction)`` are the test set.  Order: an
+    epoch is ``arange(n)``, or with ``shuffle`` ``torch.randperm(n, generator=g)`` of a CPU generator seeded with ``seed`` (successive
+    epochs continue its stream); it is uploaded ONCE per epoch (``order`` keeps the host copy) and every batch's index vector is a slice
+    of that device tensor: within an epoch nothing is copied to the device and nothing is ever read back.  A ragged last batch is
+    yielded unless ``drop_last``.  Every batch is three fresh tensors: a consumer may keep it.  ``rank`` / ``world_size``: only this
+    rank's slice of each global batch of ``batch_size`` is gathered -- ``DataParallelTrainer.shard(global_batch)``; every global batch
+    must divide evenly."""
+
+    def __init__(self, clips, batch_size, test=False, test_fraction=0.2, shuffle=False, augmentation=False, drop_last=False, seed=None,
+                 device="cuda", rank=0, world_size=1):
+        self.clips = clips if isinstance(clips, DeviceClips) else DeviceClips(clips, device)
+        self.device = self.clips.device
+        n = self.clips.num_samples
+        held_out = int(n * test_fraction)
+        self.index_offset, self.num_images = (n - held_out, held_out) if test else (0, n - held_out)
+        self.batch_size, self.shuffle, self.augmentation, self.drop_last = int(batch_size), shuffle, augmentation, drop_last
+        self.rank, self.world_size = int(rank), int(world_size)
+        if self.batch_size < 1 or self.world_size < 1 or not 0 <= self.rank < self.world_size:
+            raise ValueError("DeviceBatchLoader: batch_size %d, rank %d of %d" % (self.batch_size, self.rank, self.world_size))
+        ragged = 0 if drop_last else self.num_images % self.batch_size
+        if self.batch_size % self.world_size or ragged % self.world_size:
+            raise ValueError("DeviceBatchLoader: global batches of %d%s samples do not divide evenly over %d ranks"
+                             % (self.batch_size, " and %d" % ragged if ragged else "", self.world_size))
+        self.generator = torch.Generator()
+        if seed is None:
+            self.generator.seed()
+        else:
+            self.generator.manual_seed(seed)
+        self.order = None
+
+    def __len__(self):
+        return self.num_images // self.batch_size if self.drop_last else -(-self.num_images // self.batch_size)
+
+    def __iter__(self):
+        from . import ops
+        n = self.num_images
+        self.order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
+        order = (self.order + self.index_offset).to(self.device)               # the epoch's one upload
+        for k in range(len(self)):
+            lo = k * self.batch_size
+            per = (min(n, lo + self.batch_size) - lo) // self.world_size
+            indices = order[lo + self.rank * per:lo + (self.rank + 1) * per]
+            yield ops.gather_clips(self.clips, self.clips.samples, indices, self.clips.crop, self.augmentation)
 
 
 def render_clip(renderer, origins, low_res, upscale=4, fov=30.0, isovalue=0.34, ao_samples=0, ao_radius=0.05):

@@ -226,6 +226,11 @@ def _bind(lib):
         lib.isrBatchNormApply.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, vp]; lib.isrBatchNormApply.restype = ci
         lib.isrBatchNormGradSums.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]; lib.isrBatchNormGradSums.restype = ci
         lib.isrBatchNormBackward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]; lib.isrBatchNormBackward.restype = ci
+    if hasattr(lib, "isrClipGather"):                           # (likewise: training batches from device-resident clips, csrc/sr_dataset.hip)
+        cu = ctypes.c_uint
+        lib.isrClipGatherSupported.argtypes = [ci, ci, ci, ci, ci, ci]; lib.isrClipGatherSupported.restype = ci
+        lib.isrClipGather.argtypes = [vp, vp, vp, vp, vp, ll, vp, ci, ci, ci, ci, ci, ci, ci, cu, cu, cu, cu, ci, vp, vp, vp, vp]
+        lib.isrClipGather.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -434,7 +439,9 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  52: "discr_input_fwd_kernel", 53: "discr_input_bwd_kernel",
                  # training-mode batch normalisation (csrc/sr_batchnorm.hip): forward 54-56, backward 57-59
                  54: "batch_norm_stat_kernel", 55: "batch_norm_finish_kernel", 56: "batch_norm_apply_kernel",
-                 57: "batch_norm_grad_sum_kernel", 58: "batch_norm_grad_finish_kernel", 59: "batch_norm_backward_kernel"}
+                 57: "batch_norm_grad_sum_kernel", 58: "batch_norm_grad_finish_kernel", 59: "batch_norm_backward_kernel",
+                 # a training batch from device-resident clips (csrc/sr_dataset.hip)
+                 60: "clip_gather_kernel"}
 
 
 def debug_switches():
@@ -3240,6 +3247,103 @@ def fold_batch_norm(weight, bias, bn):
             return hit[3], hit[4]
     _fold_cache[bn] = [weakref.ref(weight), stamp, _images_epoch, w, b]
     return w, b
+
+
+# ---- training batches from device-resident clips (dataset_video.DeviceClips; csrc/sr_dataset.hip) --------------------------------------
+# ``clips``: an object with the flat fp32 buffers ``high``, ``low``, ``flow`` (every clip [T, Ch, r H, r W] / [T, Cl, H, W] / [T, 2, H, W],
+# one after the other), ``table`` (int64 [clips, 5]: the clip's element offset in each of the three, H, W), ``frames``,
+# ``low_channels``, ``high_channels``, ``upscale`` and ``high_quad_aligned`` (every high offset a multiple of four elements).
+# ``samples``: int32 [n, 4] -- clip, first row x0, first column y0 of the low-resolution crop, augmentation mode 0..3.
+_SHADED_LOW_CHANNELS = (7, 8)                      # layouts with a normal at channels 4, 5 (dataset_video.data_augmentation)
+
+
+def _clip_sign_masks(low_channels):
+    """(low, flow) x (row flip, column flip): bit ch set = the flip negates channel ch."""
+    shaded = low_channels in _SHADED_LOW_CHANNELS
+    return (1 << 4 if shaded else 0, 1 << 5 if shaded else 0), (1 << 0, 1 << 1)
+
+
+def _gather_operands(clips, samples, indices, crop):
+    buffers = (clips.high, clips.low, clips.flow)
+    if any(t.dtype != torch.float32 for t in buffers):
+        raise ValueError("gather_clips: the clip buffers must be fp32, got %s" % ([str(t.dtype) for t in buffers],))
+    if clips.table.dtype != torch.int64 or samples.dtype != torch.int32 or indices.dtype != torch.int64:
+        raise ValueError("gather_clips: the clip table and the indices are int64, the sample table is int32")
+    devices = {t.device for t in buffers + (clips.table, samples, indices)}
+    if len(devices) != 1:
+        raise ValueError("gather_clips: operands on more than one device: %s" % sorted(str(d) for d in devices))
+    if samples.dim() != 2 or samples.shape[1] != 4 or samples.shape[0] < 1 or indices.dim() != 1 or clips.table.dim() != 2 or clips.table.shape[1] != 5:
+        raise ValueError("gather_clips: expected samples [n >= 1, 4], indices [B] and a clip table [clips, 5]")
+    if int(crop) < 1:
+        raise ValueError("gather_clips: crop must be positive")
+
+
+def gather_clips_supported(clips, samples, indices, crop):
+    """Does ``gather_clips`` run the HIP kernel?  Device operands, a library that has the entry point and a batch it takes."""
+    if not (clips.high.is_cuda and all(t.is_contiguous() for t in (clips.high, clips.low, clips.flow, clips.table, samples, indices))):
+        return False
+    lib = _sr()
+    return hasattr(lib, "isrClipGather") and bool(lib.isrClipGatherSupported(indices.shape[0], clips.frames, clips.low_channels,
+                                                                             clips.high_channels, int(crop), clips.upscale))
+
+
+def _gather_clips_torch(clips, samples, indices, crop, augment):
+    # THE DEFINITION: DatasetFromSamples.__getitem__ + data_augmentation + the default collate, on the flat buffers
+    T, r = clips.frames, clips.upscale
+    rows = samples[indices.clamp(0, samples.shape[0] - 1)].tolist()
+    table = clips.table.tolist()
+    (low_x, low_y), (flow_x, flow_y) = _clip_sign_masks(clips.low_channels)
+    parts = ([], [], [])
+    for clip, x0, y0, mode in rows:
+        off_high, off_low, off_flow, H, W = table[clip]
+        flip_x, flip_y = bool(augment and mode & 1), bool(augment and mode & 2)
+        dims = [d for d, f in ((2, flip_x), (3, flip_y)) if f]
+        for out, buf, off, C, s, neg_x, neg_y in ((parts[0], clips.low, off_low, clips.low_channels, 1, low_x, low_y),
+                                                  (parts[1], clips.flow, off_flow, 2, 1, flow_x, flow_y),
+                                                  (parts[2], clips.high, off_high, clips.high_channels, r, 0, 0)):
+            t = buf[off:off + T * C * s * H * s * W].view(T, C, s * H, s * W)[:, :, s * x0:s * (x0 + crop), s * y0:s * (y0 + crop)]
+            t = t.flip(dims) if dims else t.clone()
+            for ch in range(C):
+                if flip_x and (neg_x >> ch) & 1: t[:, ch] = -t[:, ch]
+                if flip_y and (neg_y >> ch) & 1: t[:, ch] = -t[:, ch]
+            out.append(t)
+    hr = r * crop
+    shapes = ((0, T, clips.low_channels, crop, crop), (0, T, 2, crop, crop), (0, T, clips.high_channels, hr, hr))
+    return tuple(torch.stack(p) if p else torch.empty(sh, dtype=torch.float32, device=clips.high.device) for p, sh in zip(parts, shapes))
+
+
+def gather_clips(clips, samples, indices, crop, augment=False):
+    """The training batch ``(input [B, T, Cl, c, c], flow [B, T, 2, c, c], target [B, T, Ch, r c, r c])`` of the samples ``indices``
+    (int64 [B]) of device-resident clips: per sample the crop ``[x0:x0 + c, y0:y0 + c]`` of low and flow and r times that box of high,
+    all T frames; with ``augment`` mode bit 0 reverses the rows and bit 1 the columns, and the flips negate flow channel 0 / 1 and, in the
+    shaded layouts (7 or 8 low channels), low channel 4 / 5 -- ``DatasetFromSamples.__getitem__`` + ``data_augmentation`` + the default
+    collate, bit for bit (-0.0 where a zero is negated).  An index outside [0, n - 1] is clamped.  Device operands: ONE launch of
+    ``clip_gather_kernel`` on the current stream into fresh tensors, no host read.  CPU operands: the definition in plain torch.  A
+    device whose library lacks the entry point runs the definition too -- after a warning, once."""
+    _gather_operands(clips, samples, indices, crop)
+    crop = int(crop)
+    if not clips.high.is_cuda:
+        return _gather_clips_torch(clips, samples, indices, crop, augment)
+    B = indices.shape[0]
+    if B == 0 or not gather_clips_supported(clips, samples, indices, crop):
+        if B:
+            _warn_once("gather_clips", "gather_clips: the loaded library has no isrClipGather for this batch (%d samples, crop %d); the "
+                       "PyTorch definition runs instead, sample by sample" % (B, crop))
+        return _gather_clips_torch(clips, samples, indices, crop, augment)
+    lib = _sr()
+    T, Cl, Ch, r = clips.frames, clips.low_channels, clips.high_channels, clips.upscale
+    dev = clips.high.device
+    inp = torch.empty((B, T, Cl, crop, crop), dtype=torch.float32, device=dev)
+    flow = torch.empty((B, T, 2, crop, crop), dtype=torch.float32, device=dev)
+    target = torch.empty((B, T, Ch, r * crop, r * crop), dtype=torch.float32, device=dev)
+    (low_x, low_y), (flow_x, flow_y) = _clip_sign_masks(Cl)
+    with torch.cuda.device(dev):
+        rc = lib.isrClipGather(_ptr(clips.high), _ptr(clips.low), _ptr(clips.flow), _ptr(clips.table), _ptr(samples), samples.shape[0],
+                               _ptr(indices), B, T, Cl, Ch, crop, r, 1 if augment else 0, low_x, low_y, flow_x, flow_y,
+                               1 if clips.high_quad_aligned else 0, _ptr(inp), _ptr(flow), _ptr(target), _stream())
+    if rc != 0:
+        raise RuntimeError("isrClipGather failed (%d)" % rc)
+    return inp, flow, target
 
 
 # ---- the viewer's display stage (viewer.py) --------------------------------------------------------------------------------------------

@@ -444,7 +444,8 @@ def fit_adversarial(model, criterion, train_loader, test_loader, modeldir, n_epo
     optimizer objects, :367-371, whose discriminator parameters are copies nothing else uses).  Returns (model, history) -- per epoch
     the four means of ``trainAdv_v2`` (:626-629: sums over batches / (batches x frames)), the learning rates, ``evaluate``'s dict and
     the checkpoint path.  The steps run eagerly (``GraphedAdversarialStep`` is the captured form of one step, for a loop with fixed batch
-    shapes)."""
+    shapes).  The loaders are any iterables of (input, flow, target) batches; ``dataset_video.DeviceBatchLoader`` is the fast path (the
+    clips resident on the device, a batch one gather launch: ``.to(device)`` below is then a no-op)."""
     if device is None:
         device = next(model.parameters()).device
     start = 1
@@ -718,7 +719,8 @@ def evaluate(model, criterion, loader, device, initial_image="zero", upscale=4, 
     """``test(epoch)`` of mainVideoUnshaded.py:639-726: the clip recurrence without gradients over the held-out
     batches; returns ``{'total_loss', 'psnr', "('l1', 'mask')", ...}`` averaged over batches x frames, with
     ``psnr = 10 log10(1 / max(1e-10, mse_color))`` per frame (``:693``).  The reference reads every term of every frame
-    back with ``.item()``; here everything is accumulated on the device and read once."""
+    back with ``.item()``; here everything is accumulated on the device and read once.  ``loader``: any iterable of batches;
+    ``dataset_video.DeviceBatchLoader(test=True)`` is the fast path (no host slicing, collating or copying per batch)."""
     was_training = model.training
     model.eval()
     feed_inputs = getattr(criterion, 'uses_input', True)
@@ -801,7 +803,12 @@ def fit(model, criterion, train_loader, test_loader, modeldir, n_epochs, paramet
     checkpoint (``initialImage``, ``upsample``, ...; ``inference.LoadedModel`` reads it).  ``restore``: continue from
     the newest (or ``restore_epoch``) checkpoint of ``modeldir``, taking model, optimizer and scheduler from it.
     Returns (model, history) -- history = one dict per epoch with the mean training loss, the learning rate, the test
-    dict of ``evaluate`` and the checkpoint path.  ``kw`` goes to ``clip_loss`` (initial_image, upscale, ...)."""
+    dict of ``evaluate`` and the checkpoint path.  ``kw`` goes to ``clip_loss`` (initial_image, upscale, ...).
+
+    ``train_loader`` / ``test_loader``: any iterables of (input, flow, target) batches.  A ``DataLoader`` over
+    ``dataset_video.DatasetFromSamples`` is the reference's feed and costs more host time per batch than the captured step takes on
+    the GPU; ``dataset_video.DeviceBatchLoader`` is the fast path -- the clips uploaded once, a batch one gather launch, the same split,
+    order and bits (``.to(device)`` below is then a no-op; profiles/device_dataset.md)."""
     if device is None:
         device = next(model.parameters()).device
     on_gpu = str(device).startswith("cuda")
