@@ -48,7 +48,8 @@ def test_tail_matches_the_three_kernel_path_and_fp64(h, w):
     scale = max(1.0, pre.abs().max().item())
     err_t = (raw_t.double().cpu() - ref).abs().max().item()
     err_s = (raw_s.double().cpu() - ref).abs().max().item()
-    # the normalised normal amplifies errors of short vectors: compare where the normal is not degenerate
+    # every pixel is compared: the normalised normal amplifies the convolutions' error where the vector is short, and on these inputs
+    # the bounds hold all the same (tests/test_frame_boundary_gpu.py asserts a lower bound on the length instead of relying on that)
     assert err_s <= 2e-5 * scale, err_s
     assert err_t <= 2e-5 * scale and err_t <= 4 * err_s + 2e-6, (err_t, err_s)
     assert (raw_t - raw_s).abs().max().item() <= 2e-5 * scale
