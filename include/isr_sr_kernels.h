@@ -185,6 +185,34 @@ int isrLossUnshadedBackward(const float* gt, const float* pred, const float* pre
                             const float* weights15, unsigned enabled, const float* shading12, float ao_strength, int inverse_ao,
                             const float* gvalues16, float* gpred, float* gprev, void* stream);
 
+/* The downsample-consistency terms of LossNetUnshaded (SuperresolutionNetwork/losses/lossnet_unshaded.py:63-70,258-282 with
+ * lossbuilder.py:343-377, `l2-ds` / `l1-ds`): loss(sample(a), sample(b)) with sample = bilinear resize by 1/4 (align_corners=False),
+ * which is the mean of the centre 2 x 2 pixels (rows / columns 4i+1, 4i+2) of every 4 x 4 cell, and the mean over the low-resolution
+ * tensor.  pred [N][6][H][W] (mask, normal xyz, depth, ao), input [N][5][H][W] (the upsampled low-resolution input: mask, normal xyz,
+ * depth), gate g = clamp(input mask / 2 + 1/2, 0, 1):
+ *   target 0 mask    a = input mask                       b = pred mask
+ *          1 normal  a = input normal / max(|.|, 1e-7) g  b = pred normal / max(|.|, 1e-7) g
+ *          2 depth   a = input depth g                    b = pred depth g
+ *          3 colour  a = the loss shader of input, ao factor 1     b = the loss shader of pred (ao_strength, inverse_ao)
+ * A border of `pad` pixels of pred -- NOT of input -- is treated as zeroed: such a pixel contributes the fields of six zero channels
+ * (the shader of a zero pixel is not 0) and receives no gradient.  weights8 / enabled bit: index kind * 4 + target, kind 0 l2, 1 l1.
+ * shading12, ao_strength, inverse_ao as isrLossUnshadedForward takes them.  isrLossDownsampleSupported: H % 4 == 0, W % 4 == 0 and
+ * 2 pad < min(H, W).  pred, input and gpred must be 16-byte aligned (else -1, nothing is launched).
+ * Forward: values8 (device) = the eight means (0 for terms that are not enabled); *total (device, in/out) += sum of weight * mean, so
+ * that the call continues the total that isrLossUnshadedForward wrote on the same stream.  workspace: isrLossDownsampleWorkspace()
+ * bytes.  Two launches, no atomics, nothing read on the host: the same bits on every run, and capturable.
+ * Backward: gtotal (device) is d L / d total; ADDS d L / d pred of the enabled terms into gpred [N][6][H][W] at the four centre pixels
+ * of every cell that lie inside the border and touches no other element -- on the stream on which isrLossUnshadedBackward has written
+ * gpred, or after a zero fill.  l1: sgn(0) = 0; clamps, |x|' and the normalisation as in isrLossUnshadedBackward.
+ * 0 ok, -1 bad arguments, -2 launch failure. */
+int isrLossDownsampleSupported(int N, int H, int W, int pad);
+long long isrLossDownsampleWorkspace(void);
+int isrLossDownsampleForward(const float* pred, const float* input, int N, int H, int W, int pad, const float* weights8, unsigned enabled,
+                             const float* shading12, float ao_strength, int inverse_ao, void* workspace, float* values8, float* total,
+                             void* stream);
+int isrLossDownsampleBackward(const float* pred, const float* input, int N, int H, int W, int pad, const float* weights8, unsigned enabled,
+                              const float* shading12, float ao_strength, int inverse_ao, const float* gtotal, float* gpred, void* stream);
+
 /* Inputs of the discriminators of the adversarial terms (SuperresolutionNetwork/losses/lossnet_unshaded.py:313-354, :414-495), one
  * launch each way.  out [N][C][H][W] = the parts that are present in the order in_a, in_b ([N][5][H][W], the upsampled input and the
  * warped previous input, or NULL), part8(cur), part8(prev) (cur, prev [N][6][H][W]; prev or NULL): C = 26 (all four), 16 (cur + prev)

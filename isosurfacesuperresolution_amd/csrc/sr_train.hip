@@ -526,6 +526,189 @@ int fill_loss_params(LossParams& P, const float* gt, const float* pred, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Downsample-consistency terms of LossNetUnshaded (lossnet_unshaded.py:63-70,258-282, lossbuilder.py:343-377):
+//   l{1,2}(sample(a), sample(b)),  sample = bilinear x 1/4 (align_corners=False) = the mean of the centre 2 x 2 pixels of each 4 x 4 cell
+// a from the upsampled input (5 channels, NOT padded, shaded with AO factor 1), b from the prediction with its border zeroed; both
+// gated by the INPUT's mask.  The fields are eval_fields / backprop_fields of the loss above.  One thread owns a cell: it reads the
+// two centre rows as aligned quads, so the forward has no shared operand and the backward no shared destination.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int DS_TERMS = 8;           // kind * 4 + target;  kind: 0 l2, 1 l1;  target: 0 mask 1 normal 2 depth 3 colour
+constexpr int DS_MAX_BLOCKS = 512;
+
+struct DsParams {
+    LossParams L;             // the shader's constants; pred, gpred, N H W pad
+    const float* input;       // [N][5][H][W]
+    float weight[DS_TERMS];
+    unsigned enabled;
+    float* partial;           // [blocks][DS_TERMS]
+    float* values;            // [DS_TERMS]
+    float* total;             // in / out
+    const float* gtotal;      // backward
+    int blocks;
+};
+
+// the mean of the centre 2 x 2 pixels as F.interpolate forms it: 0.5 * (0.5 * p00 + 0.5 * p01) + 0.5 * (0.5 * p10 + 0.5 * p11)
+__device__ __forceinline__ float centre_mean(const float (&v)[4]) { return 0.25f * ((v[0] + v[1]) + (v[2] + v[3])); }
+
+template <bool BACKWARD>
+__global__ __launch_bounds__(256) void loss_downsample_kernel(DsParams D)
+{
+    const LossParams& P = D.L;
+    const int CW = P.W / 4, CH = P.H / 4;
+    const long long cellsPerImage = (long long)CW * CH;
+    const long long cells = cellsPerImage * P.N;
+    const size_t plane = (size_t)P.H * P.W;
+    float sums[DS_TERMS];
+#pragma unroll
+    for (int t = 0; t < DS_TERMS; ++t) sums[t] = 0.f;
+
+    float coef[DS_TERMS];        // backward: weight * d mean / d sum, times the upstream gradient
+    if (BACKWARD) {
+        const float go = D.gtotal[0];
+        const float n1 = (float)((double)P.N * CH * CW), n3 = 3.0f * n1;
+#pragma unroll
+        for (int t = 0; t < DS_TERMS; ++t) {
+            const int target = t % 4;
+            const float cnt = (target == 1 || target == 3) ? n3 : n1;
+            coef[t] = ((D.enabled >> t) & 1u) ? go * D.weight[t] / cnt : 0.f;
+        }
+    }
+
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < cells; q += (long long)gridDim.x * 256) {
+        const int img = (int)(q / cellsPerImage);
+        const long long r = q % cellsPerImage;
+        const int Y0 = 4 * (int)(r / CW) + 1, X0 = 4 * (int)(r % CW);
+        const size_t basePred = (size_t)img * 6 * plane + (size_t)Y0 * P.W + X0;
+        const size_t baseIn = (size_t)img * 5 * plane + (size_t)Y0 * P.W + X0;
+        float4 p4[2][6], i4[2][5];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) p4[a][c] = *reinterpret_cast<const float4*>(P.pred + basePred + c * plane + (size_t)a * P.W);
+#pragma unroll
+            for (int c = 0; c < 5; ++c) i4[a][c] = *reinterpret_cast<const float4*>(D.input + baseIn + c * plane + (size_t)a * P.W);
+        }
+        // field components: [0] mask, [1..3] normal, [4] depth, [5..7] colour, of the four centre pixels
+        float fa[8][4], fb[8][4];
+        Fields fpred[4];
+        float gate[4];
+        bool inside[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int a = k >> 1, xk = 1 + (k & 1);
+            const int Y = Y0 + a, X = X0 + xk;
+            inside[k] = Y >= P.pad && Y < P.H - P.pad && X >= P.pad && X < P.W - P.pad;
+            float p[6], in[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) p[c] = inside[k] ? reinterpret_cast<const float*>(&p4[a][c])[xk] : 0.f;
+#pragma unroll
+            for (int c = 0; c < 5; ++c) in[c] = reinterpret_cast<const float*>(&i4[a][c])[xk];
+            in[5] = 0.f;
+            gate[k] = clamp01(in[0] * 0.5f + 0.5f);
+            Fields fi;
+            eval_fields(P, in, gate[k], fi);
+            eval_fields(P, p, gate[k], fpred[k]);
+            fa[0][k] = fi.m; fa[1][k] = fi.n[0]; fa[2][k] = fi.n[1]; fa[3][k] = fi.n[2]; fa[4][k] = fi.d;
+            fb[0][k] = fpred[k].m; fb[1][k] = fpred[k].n[0]; fb[2][k] = fpred[k].n[1]; fb[3][k] = fpred[k].n[2]; fb[4][k] = fpred[k].d;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                fa[5 + c][k] = clamp01(P.bg[c] + fi.t * (fi.cb[c] - P.bg[c]));        // five input channels: the shader's AO factor is 1
+                fb[5 + c][k] = fpred[k].col[c];
+            }
+        }
+        float d[8];       // differences b - a of the means (the scaling by 0.25 is exact: equal sums give 0 with or without contraction)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) d[c] = centre_mean(fb[c]) - centre_mean(fa[c]);
+        constexpr int tgt[8] = {0, 1, 1, 1, 2, 3, 3, 3};
+        if (!BACKWARD) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                sums[0 + tgt[c]] += d[c] * d[c];
+                sums[4 + tgt[c]] += fabsf(d[c]);
+            }
+        } else {
+            float up[8];          // d L / d (field component of ONE centre pixel of pred): a quarter of d L / d mean
+#pragma unroll
+            for (int c = 0; c < 8; ++c) up[c] = 0.25f * (2.f * coef[0 + tgt[c]] * d[c] + coef[4 + tgt[c]] * sgn(d[c]));
+            const FieldGrad fg = {up[0], {up[1], up[2], up[3]}, 0.f, up[4], {up[5], up[6], up[7]}};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (!inside[k]) continue;          // a zeroed border pixel: no gradient
+                const int a = k >> 1, xk = 1 + (k & 1);
+                float gx[6];
+                backprop_fields(P, fpred[k], gate[k], fg, gx);
+                float* dst = P.gpred + basePred + (size_t)a * P.W + xk;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) dst[c * plane] += gx[c];
+            }
+        }
+    }
+
+    if (!BACKWARD) {
+        __shared__ float red[4][DS_TERMS];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int t = 0; t < DS_TERMS; ++t) {
+            float s = sums[t];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+            if (lane == 0) red[wave][t] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < DS_TERMS)
+            D.partial[(size_t)blockIdx.x * DS_TERMS + threadIdx.x] =
+                (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    }
+}
+
+// one workgroup of 8 waves: wave t sums term t over the blocks in a fixed order, thread 0 adds the weighted means to the total
+__global__ __launch_bounds__(512) void loss_downsample_finalize_kernel(DsParams D)
+{
+    __shared__ float mean[DS_TERMS];
+    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+    float s = 0.f;
+    for (int b = lane; b < D.blocks; b += 64) s += D.partial[(size_t)b * DS_TERMS + t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) {
+        const int target = t % 4;
+        const double cnt = (double)D.L.N * (D.L.H / 4) * (D.L.W / 4) * ((target == 1 || target == 3) ? 3.0 : 1.0);
+        mean[t] = ((D.enabled >> t) & 1u) ? (float)((double)s / cnt) : 0.f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float sum = 0.f;
+        for (int k = 0; k < DS_TERMS; ++k) {
+            D.values[k] = mean[k];
+            if ((D.enabled >> k) & 1u) sum += D.weight[k] * mean[k];
+        }
+        D.total[0] += sum;
+    }
+}
+
+bool loss_downsample_shape_ok(int N, int H, int W, int pad)
+{
+    return N > 0 && H > 0 && W > 0 && !(H & 3) && !(W & 3) && pad >= 0 && 2 * pad < H && 2 * pad < W;
+}
+
+int fill_ds_params(DsParams& D, const float* pred, const float* input, int N, int H, int W, int pad, const float* weights8, unsigned enabled,
+                   const float* shading12, float ao_strength, int inverse_ao)
+{
+    if (!input || !weights8 || !loss_downsample_shape_ok(N, H, W, pad) || !aligned16(input)) return -1;
+    const float none[LOSS_TERMS] = {};
+    // (pred stands in for gt: only the shader's constants and the geometry of L are read)
+    if (int rc = fill_loss_params(D.L, pred, pred, nullptr, N, H, W, pad, none, 0u, shading12, ao_strength, inverse_ao)) return rc;
+    D.input = input;
+    for (int t = 0; t < DS_TERMS; ++t) D.weight[t] = weights8[t];
+    D.enabled = enabled & ((1u << DS_TERMS) - 1u);
+    const long long cells = (long long)N * (H / 4) * (W / 4);
+    const long long blocks = (cells + 255) / 256;
+    D.blocks = (int)(blocks > DS_MAX_BLOCKS ? DS_MAX_BLOCKS : blocks);
+    D.partial = nullptr; D.values = nullptr; D.total = nullptr; D.gtotal = nullptr;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Discriminator inputs of the adversarial terms (lossnet_unshaded.py:313-354 generator side, :414-495 train_discriminator):
 //   out = cat(in_a?, in_b?, part8(cur), part8(prev)?) with a zeroed border of `pad` pixels
 //   part8(x) = mask, normalize(normal), {colour, ao | ao, colour},  colour = the loss shader of (mask, normal', depth, ao),
@@ -1128,6 +1311,34 @@ int isrLossUnshadedBackward(const float* gt, const float* pred, const float* pre
     if (int rc = fill_loss_params(P, gt, pred, prev, N, H, W, pad, weights15, enabled, shading12, ao_strength, inverse_ao)) return rc;
     P.gout = gvalues16; P.gpred = gpred; P.gprev = gprev;
     hipLaunchKernelGGL(loss_unshaded_kernel<true>, dim3(P.blocks), dim3(256), 0, (hipStream_t)stream, P);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrLossDownsampleSupported(int N, int H, int W, int pad) { return loss_downsample_shape_ok(N, H, W, pad) ? 1 : 0; }
+
+long long isrLossDownsampleWorkspace(void) { return (long long)DS_MAX_BLOCKS * DS_TERMS * sizeof(float); }
+
+int isrLossDownsampleForward(const float* pred, const float* input, int N, int H, int W, int pad, const float* weights8, unsigned enabled,
+                             const float* shading12, float ao_strength, int inverse_ao, void* workspace, float* values8, float* total,
+                             void* stream)
+{
+    DsParams D;
+    if (!workspace || !values8 || !total) return -1;
+    if (int rc = fill_ds_params(D, pred, input, N, H, W, pad, weights8, enabled, shading12, ao_strength, inverse_ao)) return rc;
+    D.partial = (float*)workspace; D.values = values8; D.total = total;
+    hipLaunchKernelGGL(loss_downsample_kernel<false>, dim3(D.blocks), dim3(256), 0, (hipStream_t)stream, D);
+    hipLaunchKernelGGL(loss_downsample_finalize_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, D);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int isrLossDownsampleBackward(const float* pred, const float* input, int N, int H, int W, int pad, const float* weights8, unsigned enabled,
+                              const float* shading12, float ao_strength, int inverse_ao, const float* gtotal, float* gpred, void* stream)
+{
+    DsParams D;
+    if (!gtotal || !gpred || !aligned16(gpred)) return -1;
+    if (int rc = fill_ds_params(D, pred, input, N, H, W, pad, weights8, enabled, shading12, ao_strength, inverse_ao)) return rc;
+    D.gtotal = gtotal; D.L.gpred = gpred;
+    hipLaunchKernelGGL(loss_downsample_kernel<true>, dim3(D.blocks), dim3(256), 0, (hipStream_t)stream, D);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

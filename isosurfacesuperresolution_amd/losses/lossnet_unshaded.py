@@ -14,6 +14,12 @@ static ``pad``) for the l1 / mse(l2) / temp-l2 terms of the README recipe
   (``:236-256``); colours come from an internal shader with fov 30, light (0,0,1), white material,
   specular off, strengths from ``opt.lossAmbient / lossDiffuse / lossSpecular / lossAO`` (``:116-126``);
 * ``temp-l2`` compares against the warped previous prediction (``:357-388``);
+* the downsample-consistency terms ``l2-ds`` / ``l1-ds`` on mask / normal / depth / color (``:63-70``, ``:258-282``): the l2 / l1 loss
+  between the upsampled INPUT and the prediction, both resized by 1 / upscale_factor (bilinear: with factor 4 the mean of the centre
+  2 x 2 pixels of every 4 x 4 cell), normal and depth gated by the INPUT's mask, the input shaded with AO factor 1 (it has five
+  channels) and NOT padded, so the zeroed border of the prediction contributes.  Target ``ao`` raises: the reference's own forward
+  cannot run it (``input_ao = None``, ``:225``).  On the GPU two launches forward and one backward in the fused loss's autograd node
+  (``ops.loss_unshaded_ds``);
 * the adversarial terms ``adv`` / ``gan`` (spatio-temporal, 26 channels), ``tgan`` (temporal, 16) and ``sgan`` (spatial, 13), target
   ``all`` (``:80-105``, ``:313-354``): each owns a discriminator built by ``LossBuilder.gan_loss(opt.discriminator, ...)`` and adds
   ``weight * BCE-with-logits(discriminator(input), 1)`` to the generator's loss; ``train_discriminator`` (``:414-495``) is the
@@ -21,7 +27,8 @@ static ``pad``) for the l1 / mse(l2) / temp-l2 terms of the README recipe
   concatenate) are ``ops.discriminator_input``: one launch each way on the GPU where ``fused`` and its predicate hold, the composition
   of torch operators otherwise; the networks run on ``ops.conv3x3`` / ``ops.conv3x3_s2``.
 
-Parity: the l1 / mse / temp-l2 terms are checked against hand-derived values; the adversarial terms, ``train_discriminator`` and the
+Parity: the l1 / mse / temp-l2 terms are checked against hand-derived values; the ds terms against values recorded from the reference's
+own modules with the one name bound that its ``LossBuilder.downsample_loss`` misses (tests/golden/make_ds_fixtures.py); the adversarial terms, ``train_discriminator`` and the
 discriminators against values recorded from the reference's own modules (tests/golden/make_gan_fixtures.py, which supplies an empty
 stand-in for the ``torchvision`` import that only the VGG terms use).
 """
@@ -36,7 +43,7 @@ from ..utils import ScreenSpaceShading
 
 class LossBuilder:
     """Factory of the elementary loss modules ``LossNetUnshaded`` is assembled from (``SuperresolutionNetwork/losses/lossbuilder.py``): the
-    terms of the hot-path training recipe (``l1``, ``mse``; README.md:45-64) and the adversarial loss with the reference's two EnhanceNet
+    terms of the hot-path training recipe (``l1``, ``mse``; README.md:45-64), the downsample-consistency loss (``:343-406``) and the adversarial loss with the reference's two EnhanceNet
     discriminators (``:232-258``, ``:306-331``).  The reference's VGG perceptual / texture losses need a download of VGG19 weights
     (``lossbuilder.py:10,173``): out of scope, they raise; so do the TecoGAN discriminator and the
     Wasserstein form."""
@@ -53,8 +60,30 @@ class LossBuilder:
     def _unsupported(self, what):
         raise NotImplementedError("%s is outside the accelerated hot path (SURVEY.md section 2, row 12)" % what)
 
-    def downsample_loss(self, *a, **k):
-        self._unsupported("downsample loss")
+    class DownsampleLoss(nn.Module):
+        """``lossbuilder.py:343-377``: ``loss`` ('l1' | 'l2', with ``reduction``) between the two arguments resized by
+        ``1 / downsample_factor`` (``nn.Upsample``, ``downsample_mode``) -- is the super-resolved image, brought back to the input's
+        resolution, the image that was given?  ``gt_low_res``: the first argument already has the low resolution and is taken as it is.
+        Bilinear with factor 4 reads the centre 2 x 2 pixels of every 4 x 4 cell (source coordinate 4 d + 1.5) and is their plain mean."""
+
+        def __init__(self, loss, downsample_factor, downsample_mode, gt_low_res, reduction):
+            super().__init__()
+            self.sample = nn.Upsample(scale_factor=1.0 / downsample_factor, mode=downsample_mode)
+            if loss == 'l1':
+                self.loss = nn.L1Loss(reduction=reduction)
+            elif loss == 'l2':
+                self.loss = nn.MSELoss(reduction=reduction)
+            else:
+                raise ValueError("unknown loss: " + str(loss) + ", expected 'l1' or 'l2'")
+            self.gt_low_res = gt_low_res
+
+        def forward(self, gt, pred):
+            return self.loss(gt if self.gt_low_res else self.sample(gt), self.sample(pred))
+
+    def downsample_loss(self, loss, downsample_factor, downsample_mode='bilinear', low_res_gt=False, reduction='mean'):
+        """``lossbuilder.py:379-406``.  (As shipped the reference names its nested class without the qualifier, ``:404``, and raises
+        ``NameError`` here; this is the evident intent.)"""
+        return LossBuilder.DownsampleLoss(loss, downsample_factor, downsample_mode, low_res_gt, reduction).to(self.device)
 
     class AdversarialLoss(nn.Module):
         """``lossbuilder.py:232-258``: the non-saturating GAN loss on logits.  ``forward(x)``: the generator's loss, BCE of the
@@ -118,8 +147,10 @@ _TARGETS = ('mask', 'normal', 'color', 'ao', 'depth', 'all')
 class LossNetUnshaded(nn.Module):
     # forward() accepts the upsampled low-resolution input and its warped predecessor like the reference's; only the adversarial
     # terms read them: train.clip_loss skips producing them for a criterion without a discriminator (an instance with one sets
-    # uses_input = True)
+    # uses_input = True), and so does one with a downsample-consistency term, which reads the upsampled input alone
+    # (uses_previous_input = False: the recurrence then neither resizes nor warps input[:, j-1])
     uses_input = False
+    uses_previous_input = False
 
     def __init__(self, device, input_channels, output_channels, high_res, padding, opt):
         super().__init__()
@@ -128,7 +159,8 @@ class LossNetUnshaded(nn.Module):
         self.lazy_values = False
         # GPU tensors: the whole forward is ONE launch of isrLossUnshadedForward (+ a one-workgroup reduction) and the
         # whole backward ONE launch of isrLossUnshadedBackward (csrc/sr_train.hip) instead of ~350 PyTorch launches per
-        # frame, and each adversarial term's discriminator input is one launch each way (ops.discriminator_input);
+        # frame, the ds terms add two launches forward and one backward inside the same autograd node (ops.loss_unshaded_ds),
+        # and each adversarial term's discriminator input is one launch each way (ops.discriminator_input);
         # fused = False keeps the module path below (what the CPU runs, and what the GPU tests compare against)
         self.fused = True
         self._fused_cfg = (None, None)
@@ -143,6 +175,7 @@ class LossNetUnshaded(nn.Module):
         self.has_discriminator = False
         self.has_style_or_content_loss = False
         self.has_temporal_l2_loss = False
+        self.has_downsample_loss = False
         for entry in self.loss_list:
             if len(entry) < 2:
                 raise ValueError("illegal format for loss list: " + ':'.join(entry))
@@ -174,7 +207,19 @@ class LossNetUnshaded(nn.Module):
                     self.discriminator_clip_weights = False
                 self.has_discriminator = True
                 self.uses_input = True
-            elif name in ('l2-ds', 'l1-ds', 'perceptual', 'texture'):
+                self.uses_previous_input = True
+            elif name in ('l2-ds', 'l1-ds'):
+                # (:63-70) is the prediction, resized to the input's resolution, the input?
+                if target == 'ao':
+                    raise NotImplementedError("loss '%s:ao': the input has no ambient occlusion channel -- the reference's own forward cannot "
+                                              "run this term (it multiplies None, lossnet_unshaded.py:225,272)" % name)
+                if target == 'all':
+                    raise ValueError("loss '%s' has no target 'all'" % name)
+                loss_dict[name] = builder.downsample_loss(name[:2], getattr(opt, 'upscale_factor', 4), 'bilinear')
+                self.weight_dict[(name, target)] = weight
+                self.has_downsample_loss = True
+                self.uses_input = True
+            elif name in ('perceptual', 'texture'):
                 raise NotImplementedError("loss '%s' is outside the accelerated hot path" % name)
             else:
                 raise ValueError('unknown loss %s' % name)
@@ -236,29 +281,49 @@ class LossNetUnshaded(nn.Module):
         return ops.discriminator_input(cur, prev if parts[3] else None, input if parts[0] else None, prev_input if parts[1] else None,
                                        padding=self.padding, shading=self.shading, order=order, cur_raw_normal=cur_raw_normal)
 
-    def _forward_fused(self, gt, pred, prev):
+    def _forward_fused(self, gt, pred, prev, input=None):
         fused_weights = {k: v for k, v in self.weight_dict.items() if k[0] in ops.LOSS_KINDS}       # (the adversarial terms are added by forward)
+        ds_weights = {k: v for k, v in self.weight_dict.items() if k[0] in ops.LOSS_DS_KINDS}
         key = (tuple(self.shading.packed_parameters()), self.shading._ao, bool(self.shading.inverse_ao), self.padding,
-               tuple(sorted(fused_weights.items())))
+               tuple(sorted(fused_weights.items())), tuple(sorted(ds_weights.items())))
         if self._fused_cfg[0] != key:
-            self._fused_cfg = (key, ops.loss_unshaded_config(fused_weights, self.padding, self.shading))
-        vals = ops.loss_unshaded(gt, pred, prev if self.has_temporal_l2_loss else None, self._fused_cfg[1])
+            self._fused_cfg = (key, ops.loss_unshaded_config(fused_weights, self.padding, self.shading),
+                               ops.loss_downsample_config(ds_weights, self.padding, self.shading) if ds_weights else None)
+        prev = prev if self.has_temporal_l2_loss else None
+        if ds_weights:
+            vals = ops.loss_unshaded_ds(gt, pred, prev, input, self._fused_cfg[1], self._fused_cfg[2])
+        else:
+            vals = ops.loss_unshaded(gt, pred, prev, self._fused_cfg[1])
         host = None if self.lazy_values else vals.detach().tolist()
         values = {}
-        for kind in ('mse', 'l1', 'temp-l2'):
+        for kind in ('mse', 'l1'):
             for target in ('mask', 'normal', 'ao', 'depth', 'color'):
                 if (kind, target) in self.weight_dict:
                     t = ops.LOSS_KINDS.index(kind) * 5 + ops.LOSS_TARGETS.index(target)
                     values[(kind, target)] = vals[t].detach() if self.lazy_values else host[t]
+        for kind in ops.LOSS_DS_KINDS:
+            for target in ops.LOSS_DS_TARGETS:
+                if (kind, target) in self.weight_dict:
+                    t = 16 + ops.LOSS_DS_KINDS.index(kind) * 4 + ops.LOSS_DS_TARGETS.index(target)
+                    values[(kind, target)] = vals[t].detach() if self.lazy_values else host[t]
+        for target in ('mask', 'normal', 'ao', 'depth', 'color'):
+            if ('temp-l2', target) in self.weight_dict:
+                t = 10 + ops.LOSS_TARGETS.index(target)
+                values[('temp-l2', target)] = vals[t].detach() if self.lazy_values else host[t]
         return vals[15], values
 
     def forward(self, gt, pred, input, prev_input_warped, prev_pred_warped):
         B, Cout, Hh, Wh = gt.shape
         assert Cout == 6
         assert gt.shape == pred.shape
-        if self._fusable(gt, pred, prev_pred_warped):
-            # the fused launch computes the l1 / mse / temp-l2 part; the adversarial terms are added to its total
-            total, values = self._forward_fused(gt, pred, prev_pred_warped)
+        if self.has_downsample_loss and input is None:
+            raise ValueError("the downsample-consistency terms need the upsampled input")
+        # (a ds term whose operands the ds kernels do not take -- a height or width that is no multiple of 4, an input that needs a
+        # gradient -- sends the whole criterion down the module path for this call)
+        if self._fusable(gt, pred, prev_pred_warped) and (not self.has_downsample_loss
+                                                          or ops.loss_downsample_supported(pred, input, self.padding)):
+            # the fused launches compute the l1 / mse / temp-l2 / ds part; the adversarial terms are added to its total
+            total, values = self._forward_fused(gt, pred, prev_pred_warped, input)
             if self.has_discriminator:
                 if self._fused_inputs(pred, prev_pred_warped, input, prev_input_warped):
                     # the assembly kernel zeroes the border itself and shades: the unpadded prediction goes in
@@ -298,6 +363,25 @@ class LossNetUnshaded(nn.Module):
                     loss = self.loss_dict[name](a, b)
                     values[key] = loss.detach() if self.lazy_values else loss.item()
                     total = total + self.weight_dict[key] * loss
+
+        if self.has_downsample_loss:
+            # (:258-282) the upsampled input -- NOT padded, gated by its own mask, five channels: the shader's AO factor is 1 -- against the
+            # padded prediction: a border pixel of the prediction contributes its zeroed fields (and the shader of a zero pixel is not 0)
+            input_gate = torch.clamp(input[:, 0:1] * 0.5 + 0.5, 0, 1)
+            dfields = {
+                'mask': lambda: (input[:, 0:1], pred_mask),
+                'normal': lambda: (norm(input[:, 1:4], dim=1) * input_gate, norm(pred[:, 1:4], dim=1) * input_gate),
+                'depth': lambda: (input[:, 4:5] * input_gate, pred[:, 4:5] * input_gate),
+                'color': lambda: (self.shading(input), pred_color),
+            }
+            for name in ('l2-ds', 'l1-ds'):
+                for target in ('mask', 'normal', 'depth', 'color'):
+                    key = (name, target)
+                    if key in self.weight_dict:
+                        a, b = dfields[target]()
+                        loss = self.loss_dict[name](a, b)
+                        values[key] = loss.detach() if self.lazy_values else loss.item()
+                        total = total + self.weight_dict[key] * loss
 
         if self.has_discriminator:
             adv, adv_values = self._adversarial_terms(pred, pred_color, input, prev_input_warped, prev_pred_warped)

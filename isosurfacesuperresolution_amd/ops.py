@@ -114,6 +114,13 @@ def _bind(lib):
     lib.isrLossUnshadedForward.restype = ci
     lib.isrLossUnshadedBackward.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, ctypes.c_uint, vp, cf, ci, vp, vp, vp, vp]
     lib.isrLossUnshadedBackward.restype = ci
+    if hasattr(lib, "isrLossDownsampleForward"):      # (an older build loaded through ISR_SR_LIB for an A/B run has no ds entry points)
+        lib.isrLossDownsampleSupported.argtypes = [ci, ci, ci, ci]; lib.isrLossDownsampleSupported.restype = ci
+        lib.isrLossDownsampleWorkspace.argtypes = []; lib.isrLossDownsampleWorkspace.restype = ll
+        lib.isrLossDownsampleForward.argtypes = [vp, vp, ci, ci, ci, ci, vp, ctypes.c_uint, vp, cf, ci, vp, vp, vp, vp]
+        lib.isrLossDownsampleForward.restype = ci
+        lib.isrLossDownsampleBackward.argtypes = [vp, vp, ci, ci, ci, ci, vp, ctypes.c_uint, vp, cf, ci, vp, vp, vp]
+        lib.isrLossDownsampleBackward.restype = ci
     lib.isrDiscrInputSupported.argtypes = [ci, ci, ci, ci]; lib.isrDiscrInputSupported.restype = ci
     lib.isrDiscrInputForward.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, cf, ci, vp]
     lib.isrDiscrInputForward.restype = ci
@@ -2109,6 +2116,105 @@ def loss_unshaded_config(weight_dict, padding, shading):
 def loss_unshaded(gt, pred, prev, cfg):
     """-> values[16] (differentiable w.r.t. pred and prev through values[15], the weighted total)."""
     return _LossUnshadedFunction.apply(gt, pred, prev, cfg)
+
+
+# ---- downsample-consistency terms l2-ds / l1-ds (csrc/sr_train.hip: loss_downsample_kernel) --------------------------------------
+LOSS_DS_KINDS = ('l2-ds', 'l1-ds')
+LOSS_DS_TARGETS = ('mask', 'normal', 'depth', 'color')
+_loss_ds_ws = {}
+
+
+def _offset_ptr(t, index):
+    return ctypes.c_void_p(t.data_ptr() + index * t.element_size())
+
+
+class _LossUnshadedDsFunction(torch.autograd.Function):
+    """values[24] = the 16 of ``_LossUnshadedFunction``, the ds terms added to [15], + the 8 ds means, see ``isrLossDownsampleForward``.
+    ONE node: the ds backward adds into the ``gpred`` that ``isrLossUnshadedBackward`` has just written on the same stream."""
+
+    @staticmethod
+    def forward(ctx, gt, pred, prev, input, cfg, ds_cfg):
+        lib = _sr()
+        gt, pred = _aligned16(gt.contiguous()), _aligned16(pred.contiguous())
+        prev = _aligned16(prev.contiguous()) if prev is not None else None
+        input = _aligned16(input.contiguous())
+        n, _, h, w = pred.shape
+        key = (pred.device, torch.cuda.current_stream().cuda_stream)
+        ws = _loss_ws.get(key)
+        if ws is None:
+            ws = torch.empty(lib.isrLossUnshadedWorkspace(), dtype=torch.uint8, device=pred.device)
+            _loss_ws[key] = ws
+        ds_ws = _loss_ds_ws.get(key)
+        if ds_ws is None:
+            ds_ws = torch.empty(lib.isrLossDownsampleWorkspace(), dtype=torch.uint8, device=pred.device)
+            _loss_ds_ws[key] = ds_ws
+        values = torch.empty(24, dtype=torch.float32, device=pred.device)
+        rc = lib.isrLossUnshadedForward(_ptr(gt), _ptr(pred), _ptr(prev), n, h, w, cfg['pad'], cfg['weights'], cfg['enabled'],
+                                        cfg['shading'], cfg['ao'], cfg['inverse_ao'], _ptr(ws), _ptr(values), _stream())
+        if rc != 0:
+            raise RuntimeError("isrLossUnshadedForward failed (%d)" % rc)
+        rc = lib.isrLossDownsampleForward(_ptr(pred), _ptr(input), n, h, w, ds_cfg['pad'], ds_cfg['weights'], ds_cfg['enabled'],
+                                          ds_cfg['shading'], ds_cfg['ao'], ds_cfg['inverse_ao'], _ptr(ds_ws), _offset_ptr(values, 16),
+                                          _offset_ptr(values, 15), _stream())
+        if rc != 0:
+            raise RuntimeError("isrLossDownsampleForward failed (%d)" % rc)
+        ctx.cfg, ctx.ds_cfg = cfg, ds_cfg
+        ctx.save_for_backward(gt, pred, prev, input)
+        return values
+
+    @staticmethod
+    def backward(ctx, gvalues):
+        lib = _sr()
+        gt, pred, prev, input = ctx.saved_tensors
+        cfg, ds_cfg = ctx.cfg, ctx.ds_cfg
+        n, _, h, w = pred.shape
+        gvalues = gvalues.contiguous()
+        gpred = torch.empty_like(pred)
+        gprev = torch.empty_like(prev) if prev is not None and ctx.needs_input_grad[2] else None
+        rc = lib.isrLossUnshadedBackward(_ptr(gt), _ptr(pred), _ptr(prev), n, h, w, cfg['pad'], cfg['weights'], cfg['enabled'],
+                                         cfg['shading'], cfg['ao'], cfg['inverse_ao'], _ptr(gvalues), _ptr(gpred), _ptr(gprev),
+                                         _stream())
+        if rc != 0:
+            raise RuntimeError("isrLossUnshadedBackward failed (%d)" % rc)
+        rc = lib.isrLossDownsampleBackward(_ptr(pred), _ptr(input), n, h, w, ds_cfg['pad'], ds_cfg['weights'], ds_cfg['enabled'],
+                                           ds_cfg['shading'], ds_cfg['ao'], ds_cfg['inverse_ao'], _offset_ptr(gvalues, 15), _ptr(gpred),
+                                           _stream())
+        if rc != 0:
+            raise RuntimeError("isrLossDownsampleBackward failed (%d)" % rc)
+        return None, gpred, gprev, None, None, None
+
+
+def loss_downsample_config(weight_dict, padding, shading):
+    """Host-side constants of the ds terms: weight_dict {('l2-ds' | 'l1-ds', target): weight} (other keys are not read), the rest as
+    ``loss_unshaded_config``."""
+    weights = [0.0] * 8
+    enabled = 0
+    for (kind, target), wgt in weight_dict.items():
+        if kind in LOSS_DS_KINDS:
+            t = LOSS_DS_KINDS.index(kind) * 4 + LOSS_DS_TARGETS.index(target)
+            weights[t] = float(wgt)
+            enabled |= 1 << t
+    sh, ao, inv = _discr_shading(shading)
+    return {'pad': int(padding), 'weights': (ctypes.c_float * 8)(*weights), 'enabled': enabled, 'shading': sh, 'ao': ao, 'inverse_ao': inv}
+
+
+def loss_downsample_supported(pred, input, padding):
+    """Whether ``loss_unshaded_ds`` has its kernels for these operands: fp32 GPU tensors [N, 6, H, W] and [N, 5, H, W] on one device,
+    an input that needs no gradient, a library that has the entry points, H and W multiples of 4 and ``2 * padding < min(H, W)``."""
+    if not (torch.is_tensor(pred) and torch.is_tensor(input) and pred.is_cuda and input.is_cuda and pred.device == input.device
+            and pred.dtype == torch.float32 and input.dtype == torch.float32 and pred.dim() == 4 and input.dim() == 4
+            and pred.shape[1] == 6 and input.shape == (pred.shape[0], 5, pred.shape[2], pred.shape[3]) and not input.requires_grad):
+        return False
+    lib = _sr()
+    return hasattr(lib, "isrLossDownsampleForward") and bool(lib.isrLossDownsampleSupported(pred.shape[0], pred.shape[2], pred.shape[3],
+                                                                                            int(padding)))
+
+
+def loss_unshaded_ds(gt, pred, prev, input, cfg, ds_cfg):
+    """``loss_unshaded`` with the downsample-consistency terms -> values[24]: [0..14] as ``loss_unshaded``, [15] the weighted total
+    INCLUDING the ds terms, [16..23] the ds means (``LOSS_DS_KINDS`` x ``LOSS_DS_TARGETS``).  Differentiable w.r.t. pred and prev
+    through values[15]; ``input`` [N, 5, H, W], the upsampled low-resolution input, gets no gradient."""
+    return _LossUnshadedDsFunction.apply(gt, pred, prev, input, cfg, ds_cfg)
 
 
 # ---- discriminator inputs of the adversarial terms (csrc/sr_train.hip: discr_input_kernel) -------------------------------------

@@ -71,7 +71,7 @@ Frame = collections.namedtuple("Frame", "j output previous_warped_loss input_hig
 
 
 def clip_recurrence(forward, input, flow, channels, target=None, initial_image="zero", upscale=4, disable_temporal=False,
-                    special_mask=True, feedback=None, fused=False, upsample=None):
+                    special_mask=True, feedback=None, fused=False, upsample=None, previous_input=True):
     """The reference's clip recurrence, stated once (mainVideoUnshaded.py:413-465 and its copies in the discriminator phase, the test
     pass, mainVideo.py:381-434 and the two statistics scripts).  input [B,T,C,h,w], flow [B,T,2,h,w]; for every frame j
 
@@ -85,17 +85,19 @@ def clip_recurrence(forward, input, flow, channels, target=None, initial_image="
     ``previous_warped_loss``: target[:,0] where a frame starts from the initial image, ``previous_warped`` elsewhere (None without a
     ``target``).  ``upsample`` (an interpolation mode): the low-resolution inputs the reference hands to its criterion
     (mainVideoUnshaded.py:432-452) -- ``input_high`` = input[:,j] upsampled, ``previous_input`` = input[:,j-1] upsampled and warped
-    (input[:,0] upsampled at a start); both None without it.  ``fused``: where ``ops.recurrent_input`` supports the operands, feedback
+    (input[:,0] upsampled at a start); both None without it; ``previous_input=False`` (a criterion that reads ``input_high`` alone,
+    ``LossNetUnshaded.uses_previous_input``) leaves ``Frame.previous_input`` None and enqueues neither its resize nor its warp.  ``fused``: where ``ops.recurrent_input`` supports the operands, feedback
     (it is ``clamp_prediction`` there), warp, space-to-depth and cat are ONE kernel on the raw output."""
     size = (input.shape[3] * upscale, input.shape[4] * upscale)
     kw = dict(mode=upsample, **({"align_corners": False} if upsample in ("bilinear", "bicubic") else {}))
-    output = input_high = previous_input = None
+    output = input_high = None
+    want_previous, previous_input = previous_input, None
     for j in range(input.shape[1]):
         single_input = None
         if j == 0 or disable_temporal:
             previous_warped = initialImage(input[:, 0], channels, initial_image, False, upscale)
             previous_warped_loss = target[:, 0] if target is not None else None
-            if upsample:
+            if upsample and want_previous:
                 previous_input = F.interpolate(input[:, 0], size=size, **kw)
         else:
             if fused and ops.recurrent_input_supported(output, input[:, j], flow[:, j - 1], upscale):
@@ -104,7 +106,7 @@ def clip_recurrence(forward, input, flow, channels, target=None, initial_image="
                 previous_output = output if feedback is None else feedback(output)
                 previous_warped = VideoTools.warp_upscale(previous_output, flow[:, j - 1], upscale, special_mask=special_mask)
             previous_warped_loss = previous_warped
-            if upsample:
+            if upsample and want_previous:
                 previous_input = VideoTools.warp_upscale(F.interpolate(input[:, j - 1], size=size, **kw), flow[:, j - 1], upscale,
                                                          special_mask=True)
         if single_input is None:
@@ -142,13 +144,14 @@ def clip_loss(model, criterion, input, flow, target, initial_image="zero", upsca
     The reference reads every frame's loss back with ``.item()`` (mainVideoUnshaded.py:454); here the sum is accumulated
     on the device and read back ONCE after the last frame, so the whole clip is enqueued without a stall."""
     _refresh_split_images(model, target)
-    # only LossNetUnshaded's adversarial terms read the upsampled inputs, so a criterion without a discriminator says so
-    # (uses_input = False) and is not fed
+    # only LossNetUnshaded's adversarial and downsample-consistency terms read the upsampled inputs, so a criterion without them
+    # says so (uses_input = False) and is not fed; the warped previous input is the adversarial terms' alone (uses_previous_input)
     feed_inputs = getattr(criterion, 'uses_input', True)
     loss, loss_sum = 0, None
     with lazy_values(criterion):
         for f in clip_recurrence(lambda x: model(x)[0], input, flow, target.shape[2], target, initial_image, upscale, disable_temporal,
-                                 feedback=clamp_prediction, fused=fused_recurrence, upsample=upsample if feed_inputs else None):
+                                 feedback=clamp_prediction, fused=fused_recurrence, upsample=upsample if feed_inputs else None,
+                                 previous_input=getattr(criterion, 'uses_previous_input', True)):
             loss0, _ = criterion(target[:, f.j], f.output, f.input_high, f.previous_input, f.previous_warped_loss)
             loss = loss + loss0
             loss_sum = loss0.detach() if loss_sum is None else loss_sum + loss0.detach()
@@ -733,7 +736,8 @@ def evaluate(model, criterion, loader, device, initial_image="zero", upscale=4, 
         for batch in loader:
             input, flow, target = (t.to(device) for t in batch)
             for f in clip_recurrence(lambda x: model(x)[0], input, flow, target.shape[2], target, initial_image, upscale, disable_temporal,
-                                     feedback=clamp_prediction, upsample=upsample if feed_inputs else None):
+                                     feedback=clamp_prediction, upsample=upsample if feed_inputs else None,
+                                     previous_input=getattr(criterion, 'uses_previous_input', True)):
                 loss0, values = criterion(target[:, f.j], f.output, f.input_high, f.previous_input, f.previous_warped_loss)
                 add('total_loss', loss0)
                 mse = values[('mse', 'color')]
