@@ -754,6 +754,31 @@ int isrClipGather(const float* high, const float* low, const float* flow, const 
                   unsigned lowNegX, unsigned lowNegY, unsigned flowNegX, unsigned flowNegY, int highQuadAligned,
                   float* input, float* flowOut, float* target, void* stream);
 
+/* The clip generator's frame packer (csrc/sr_dataset.hip: clip_pack_kernel; datagen.py).  ONE launch on `stream` writes one frame of a
+ * training clip into the flat clip buffers above, from what the ray-marcher and the flow fill left on the device:
+ *   lowGbuffer  [h][w][12], highGbuffer [r h][r w][12] : the two renders of the frame, pixel-interleaved, 16-byte aligned
+ *   flow        [2][h][w]                              : the hole-filled flow of the low render (isrFlowFill)
+ *   highBuf + highOffset <- six planes [r h][r w]: clamp(g[3], 0, 1) 2 - 1, g[4], g[5], g[6], g[7], g[10]   (mask, normal, depth, AO)
+ *   lowBuf  + lowOffset  <- five planes [h][w]   : clamp(g[3], 0, 1) 2 - 1, g[4], g[5], g[6], g[7]
+ *   flowBuf + flowOffset <- two planes [h][w]    : copied
+ * i.e. convertToNumpy of the reference's DataGenerator/DataGeneratorVideo2.py:66-77 without the files; only the alpha is clamped, as
+ * numpy's clip does it (a NaN stays a NaN); every other value keeps its bits.  The offsets are 64-bit element counts; that the frame
+ * fits behind them is the caller's responsibility.  With w a multiple of four and 16-byte aligned destinations and flow, planes are
+ * written 16 bytes per lane, otherwise float by float: the same values.  r <= 64 and at most 2^26 pixels in the high image
+ * (isrClipPackFrameSupported says so beforehand; anything else, or a misaligned G-buffer, returns -3).  No host synchronisation. */
+int isrClipPackFrameSupported(int h, int w, int r);
+int isrClipPackFrame(const float* lowGbuffer, const float* highGbuffer, const float* flow, int h, int w, int r, float* highBuf,
+                     long long highOffset, float* lowBuf, long long lowOffset, float* flowBuf, long long flowOffset, void* stream);
+
+/* Crop coverage of device-resident clips (csrc/sr_dataset.hip: clip_coverage_kernel).  ONE launch, one workgroup per (clip, frame 0 /
+ * frame T - 1): tables + tableOffsets[clip] <- int32 [2][H + 1][W + 1], the summed-area tables of the indicator
+ * (low[0] + low[1]) + low[2] > 0 (fp32, that order) of the clip's first and last low-resolution frame: entry [y][x] counts the covered
+ * pixels of rows < y and columns < x.  low, clipTable: as for isrClipGather ([T][Cl][H][W] per clip, Cl >= 3); tableOffsets: device
+ * int64 [numClips], element offsets into `tables`.  Anything else returns -3 (isrClipCoverageSupported). */
+int isrClipCoverageSupported(int numClips, int T, int Cl);
+int isrClipCoverage(const float* low, const long long* clipTable, const long long* tableOffsets, int numClips, int T, int Cl, int* tables,
+                    void* stream);
+
 /* Optional per-dispatch timing of isrConv3x3Forward for benchmarks: while enabled, every forward
  * dispatch carries a start/stop event pair on its own packet (no extra stream operations).
  * isrProfileEnable(1) clears the records and starts recording, (0) stops; (2) also records the frame's small kernels

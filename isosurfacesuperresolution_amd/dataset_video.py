@@ -115,6 +115,27 @@ class DatasetFromSamples(data.Dataset):
                 torch.from_numpy(np.ascontiguousarray(high)))
 
 
+def _sample_table(samples, rows, c, r):
+    """The int32 [n, 4] sample table of ``DeviceClips`` as a list, every sample checked against the clip rows ``(.., .., .., H, W)``."""
+    table = []
+    for j, s in enumerate(samples):
+        x0, x1, y0, y1 = (int(v) for v in s.crop_low)
+        if not 0 <= s.index < len(rows):
+            raise ValueError("DeviceClips: sample %d: clip %d of %d" % (j, s.index, len(rows)))
+        H, W = rows[s.index][3:]
+        if x1 - x0 != c or y1 - y0 != c or x0 < 0 or y0 < 0 or x1 > H or y1 > W:
+            raise ValueError("DeviceClips: sample %d: the crop rows %d:%d, columns %d:%d is not a %d x %d box inside clip %d (%d x %d)"
+                             % (j, x0, x1, y0, y1, c, c, s.index, H, W))
+        if tuple(int(v) for v in s.crop_high) != (r * x0, r * x1, r * y0, r * y1):
+            raise ValueError("DeviceClips: sample %d: the high-resolution box %s is not %d times the low-resolution one" % (j, tuple(s.crop_high), r))
+        if not 0 <= int(s.augmentation) < MAX_AUGMENTATION_MODE:
+            raise ValueError("DeviceClips: sample %d: augmentation mode %d" % (j, s.augmentation))
+        table.append((s.index, x0, y0, int(s.augmentation)))
+    if not table:
+        raise ValueError("DeviceClips: no samples")
+    return table
+
+
 class DeviceClips:
     """A ``DatasetData`` resident on ``device``: every clip uploaded ONCE, clip by clip, into three flat fp32 buffers (``high``, ``low``,
     ``flow``), plus the two tables ``ops.gather_clips`` reads -- ``table`` int64 [clips, 5] (element offset of the clip in each buffer,
@@ -147,22 +168,7 @@ class DeviceClips:
             off[0] += -(-high.size // 4) * 4              # every clip starts on a multiple of four elements: 16-byte rows for the gather
             off[1] += low.size
             off[2] += flow.size
-        table = []
-        for j, s in enumerate(dd.samples):
-            x0, x1, y0, y1 = (int(v) for v in s.crop_low)
-            if not 0 <= s.index < len(rows):
-                raise ValueError("DeviceClips: sample %d: clip %d of %d" % (j, s.index, len(rows)))
-            H, W = rows[s.index][3:]
-            if x1 - x0 != c or y1 - y0 != c or x0 < 0 or y0 < 0 or x1 > H or y1 > W:
-                raise ValueError("DeviceClips: sample %d: the crop rows %d:%d, columns %d:%d is not a %d x %d box inside clip %d (%d x %d)"
-                                 % (j, x0, x1, y0, y1, c, c, s.index, H, W))
-            if tuple(int(v) for v in s.crop_high) != (r * x0, r * x1, r * y0, r * y1):
-                raise ValueError("DeviceClips: sample %d: the high-resolution box %s is not %d times the low-resolution one" % (j, tuple(s.crop_high), r))
-            if not 0 <= int(s.augmentation) < MAX_AUGMENTATION_MODE:
-                raise ValueError("DeviceClips: sample %d: augmentation mode %d" % (j, s.augmentation))
-            table.append((s.index, x0, y0, int(s.augmentation)))
-        if not table:
-            raise ValueError("DeviceClips: no samples")
+        table = _sample_table(dd.samples, rows, c, r)
         self.nbytes = 4 * sum(off) + 8 * 5 * len(rows) + 4 * 4 * len(table)
         if self.device.type == "cuda":
             free, total = torch.cuda.mem_get_info(self.device)
@@ -177,6 +183,39 @@ class DeviceClips:
         self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)
         self.samples = torch.tensor(table, dtype=torch.int32).to(self.device)
         self.num_samples, self.num_clips = len(table), len(rows)
+
+    @classmethod
+    def from_buffers(cls, high, low, flow, table_rows, samples, frames, low_channels, high_channels, crop, upscale):
+        """ADOPT clips that already lie in flat fp32 buffers (``datagen.GeneratedClips``: rendered into them on the device) -- no copy.
+        ``table_rows``: per clip ``(high offset, low offset, flow offset, H, W)``; ``samples``: a list of ``Sample``.  The same checks
+        as the constructor's: fp32 buffers, clips inside them, every sample's box inside its clip."""
+        self = cls.__new__(cls)
+        buffers = (high, low, flow)
+        for name, t in zip(("high", "low", "flow"), buffers):
+            if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("DeviceClips: %s is %s %s, not a flat float32 buffer" % (name, t.dtype, tuple(t.shape)))
+        if len({t.device for t in buffers}) != 1:
+            raise ValueError("DeviceClips: buffers on more than one device")
+        rows = [tuple(int(v) for v in row) for row in table_rows]
+        if not rows:
+            raise ValueError("DeviceClips: no clips")
+        T, Cl, Ch, r, c = int(frames), int(low_channels), int(high_channels), int(upscale), int(crop)
+        for i, row in enumerate(rows):
+            H, W = (row[3], row[4]) if len(row) == 5 else (0, 0)
+            sizes = (T * Ch * r * H * r * W, T * Cl * H * W, T * 2 * H * W)
+            if H < 1 or W < 1 or r < 1 or T < 1 or any(not 0 <= off <= t.numel() - n for off, t, n in zip(row, buffers, sizes)):
+                raise ValueError("DeviceClips: clip %d: row %s with %d frames, %d / %d channels, upscale %d leaves the buffers (%d, %d, %d elements)"
+                                 % (i, row, T, Ch, Cl, r, high.numel(), low.numel(), flow.numel()))
+        table = _sample_table(samples, rows, c, r)
+        self.device = high.device
+        self.frames, self.low_channels, self.high_channels, self.crop, self.upscale = T, Cl, Ch, c, r
+        self.high, self.low, self.flow = buffers
+        self.high_quad_aligned = all(row[0] % 4 == 0 for row in rows)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)
+        self.samples = torch.tensor(table, dtype=torch.int32).to(self.device)
+        self.num_samples, self.num_clips = len(table), len(rows)
+        self.nbytes = 4 * (high.numel() + low.numel() + flow.numel()) + 8 * 5 * len(rows) + 4 * 4 * len(table)
+        return self
 
 
 class DeviceBatchLoader:

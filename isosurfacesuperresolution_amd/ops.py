@@ -238,6 +238,11 @@ def _bind(lib):
         lib.isrClipGatherSupported.argtypes = [ci, ci, ci, ci, ci, ci]; lib.isrClipGatherSupported.restype = ci
         lib.isrClipGather.argtypes = [vp, vp, vp, vp, vp, ll, vp, ci, ci, ci, ci, ci, ci, ci, cu, cu, cu, cu, ci, vp, vp, vp, vp]
         lib.isrClipGather.restype = ci
+    if hasattr(lib, "isrClipPackFrame"):                        # (likewise: the clip generator's frame packer and crop coverage)
+        lib.isrClipPackFrameSupported.argtypes = [ci, ci, ci]; lib.isrClipPackFrameSupported.restype = ci
+        lib.isrClipPackFrame.argtypes = [vp, vp, vp, ci, ci, ci, vp, ll, vp, ll, vp, ll, vp]; lib.isrClipPackFrame.restype = ci
+        lib.isrClipCoverageSupported.argtypes = [ci, ci, ci]; lib.isrClipCoverageSupported.restype = ci
+        lib.isrClipCoverage.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]; lib.isrClipCoverage.restype = ci
     lib.isrProfileEnable.argtypes = [ci]; lib.isrProfileEnable.restype = ci
     lib.isrProfileCount.argtypes = []; lib.isrProfileCount.restype = ci
     lib.isrProfileGet.argtypes = [ci, vp, vp, vp]; lib.isrProfileGet.restype = ci
@@ -448,7 +453,9 @@ VARIANT_NAMES = {6: "conv3x3_small_cout_kernel", 2: "conv3x3_fwd_kernel<1,false>
                  54: "batch_norm_stat_kernel", 55: "batch_norm_finish_kernel", 56: "batch_norm_apply_kernel",
                  57: "batch_norm_grad_sum_kernel", 58: "batch_norm_grad_finish_kernel", 59: "batch_norm_backward_kernel",
                  # a training batch from device-resident clips (csrc/sr_dataset.hip)
-                 60: "clip_gather_kernel"}
+                 60: "clip_gather_kernel",
+                 # the clip generator (datagen.py): a rendered frame into the flat clip buffers, crop coverage of the first / last frames
+                 61: "clip_pack_kernel", 62: "clip_coverage_kernel"}
 
 
 def debug_switches():
@@ -3450,6 +3457,129 @@ def gather_clips(clips, samples, indices, crop, augment=False):
     if rc != 0:
         raise RuntimeError("isrClipGather failed (%d)" % rc)
     return inp, flow, target
+
+
+# ---- the clip generator's device side (datagen.py; csrc/sr_dataset.hip) --------------------------------------------------------------
+PACK_HIGH_CHANNELS = (3, 4, 5, 6, 7, 10)           # mask (from alpha), normal, depth, ambient occlusion of a G-buffer pixel
+PACK_LOW_CHANNELS = (3, 4, 5, 6, 7)
+
+
+def _pack_operands(low_gbuf, high_gbuf, flow, high_buf, low_buf, flow_buf, offsets):
+    tensors = (low_gbuf, high_gbuf, flow, high_buf, low_buf, flow_buf)
+    if any(t.dtype != torch.float32 for t in tensors):
+        raise ValueError("pack_clip_frame: every operand is fp32, got %s" % ([str(t.dtype) for t in tensors],))
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError("pack_clip_frame: operands on more than one device")
+    if low_gbuf.dim() != 3 or low_gbuf.shape[2] != 12 or high_gbuf.dim() != 3 or high_gbuf.shape[2] != 12 or min(low_gbuf.shape) < 1:
+        raise ValueError("pack_clip_frame: the G-buffers are [h, w, 12] and [r h, r w, 12], got %s and %s" % (tuple(low_gbuf.shape), tuple(high_gbuf.shape)))
+    h, w = int(low_gbuf.shape[0]), int(low_gbuf.shape[1])
+    r = int(high_gbuf.shape[0]) // h
+    if r < 1 or tuple(high_gbuf.shape[:2]) != (r * h, r * w) or flow.numel() != 2 * h * w or tuple(flow.shape[-2:]) != (h, w):
+        raise ValueError("pack_clip_frame: low %s, high %s and flow %s are not [h, w, 12], [r h, r w, 12] and [2, h, w]"
+                         % (tuple(low_gbuf.shape), tuple(high_gbuf.shape), tuple(flow.shape)))
+    n = h * w
+    for name, buf, off, size in zip(("high", "low", "flow"), (high_buf, low_buf, flow_buf), offsets,
+                                    (len(PACK_HIGH_CHANNELS) * r * r * n, len(PACK_LOW_CHANNELS) * n, 2 * n)):
+        if buf.dim() != 1 or not buf.is_contiguous() or not 0 <= int(off) <= buf.numel() - size:
+            raise ValueError("pack_clip_frame: %d elements at offset %d do not fit the flat %s buffer of %s" % (size, off, name, tuple(buf.shape)))
+    return h, w, r
+
+
+def pack_clip_frame_supported(low_gbuf, high_gbuf, flow):
+    """Does ``pack_clip_frame`` run the HIP kernel?  Contiguous device operands, 16-byte aligned G-buffers, a library that has the entry
+    point and a frame it takes."""
+    if not (low_gbuf.is_cuda and all(t.is_contiguous() for t in (low_gbuf, high_gbuf, flow))) or low_gbuf.data_ptr() % 16 or high_gbuf.data_ptr() % 16:
+        return False
+    lib = _sr()
+    return hasattr(lib, "isrClipPackFrame") and bool(lib.isrClipPackFrameSupported(low_gbuf.shape[0], low_gbuf.shape[1],
+                                                                                   high_gbuf.shape[0] // low_gbuf.shape[0]))
+
+
+def _pack_clip_frame_torch(low_gbuf, high_gbuf, flow, high_buf, low_buf, flow_buf, offsets):
+    # THE DEFINITION: convertToNumpy of DataGenerator/DataGeneratorVideo2.py:66-77 on G-buffers instead of EXR files.  Only the alpha is
+    # clipped (torch.clamp keeps a NaN, as np.clip does); normals, depth and AO are copied.
+    for gbuf, channels, buf, off in ((high_gbuf, PACK_HIGH_CHANNELS, high_buf, int(offsets[0])), (low_gbuf, PACK_LOW_CHANNELS, low_buf, int(offsets[1]))):
+        planes = gbuf.permute(2, 0, 1)[list(channels)].clone()
+        planes[0] = planes[0].clamp(0, 1) * 2 - 1
+        buf[off:off + planes.numel()].copy_(planes.reshape(-1))
+    flow_buf[int(offsets[2]):int(offsets[2]) + flow.numel()].copy_(flow.reshape(-1))
+
+
+def pack_clip_frame(low_gbuf, high_gbuf, flow, high_buf, low_buf, flow_buf, offsets):
+    """One frame of a training clip from its two renders: the G-buffers ``low_gbuf`` [h, w, 12] and ``high_gbuf`` [r h, r w, 12] and the
+    hole-filled ``flow`` [2, h, w] (or [1, 2, h, w]) into the flat fp32 buffers at the element ``offsets`` (high, low, flow) -- six planes
+    ``[clamp(g[3], 0, 1) 2 - 1, g[4], g[5], g[6], g[7], g[10]]`` of the high render, five ``[clamp(g[3], 0, 1) 2 - 1, g[4..7]]`` of the low
+    one, the flow copied: the reference's ``convertToNumpy``.  Device operands: ONE launch of ``clip_pack_kernel`` on the current stream,
+    no host read.  CPU operands: the definition in plain torch.  A device whose library lacks the entry point, or operands the kernel
+    does not take, run the definition too -- after a warning, once."""
+    _pack_operands(low_gbuf, high_gbuf, flow, high_buf, low_buf, flow_buf, offsets)
+    if low_gbuf.is_cuda and pack_clip_frame_supported(low_gbuf, high_gbuf, flow):
+        h, w = low_gbuf.shape[0], low_gbuf.shape[1]
+        with torch.cuda.device(low_gbuf.device):
+            rc = _sr().isrClipPackFrame(_ptr(low_gbuf), _ptr(high_gbuf), _ptr(flow), h, w, high_gbuf.shape[0] // h, _ptr(high_buf), int(offsets[0]),
+                                        _ptr(low_buf), int(offsets[1]), _ptr(flow_buf), int(offsets[2]), _stream())
+        if rc != 0:
+            raise RuntimeError("isrClipPackFrame failed (%d)" % rc)
+        return
+    if low_gbuf.is_cuda:
+        _warn_once("pack_clip_frame", "pack_clip_frame: the loaded library has no isrClipPackFrame for these operands (low %s); the PyTorch "
+                   "definition runs instead" % (tuple(low_gbuf.shape),))
+    _pack_clip_frame_torch(low_gbuf, high_gbuf, flow, high_buf, low_buf, flow_buf, offsets)
+
+
+def coverage_table_offsets(rows):
+    """Element offset of every clip's pair of tables in the flat result of ``clip_coverage``, and its length: ``rows`` is the clip
+    table as a list; clip k takes 2 (H + 1) (W + 1) elements."""
+    offsets, total = [], 0
+    for row in rows:
+        offsets.append(total)
+        total += 2 * (int(row[3]) + 1) * (int(row[4]) + 1)
+    return offsets, total
+
+
+def _clip_coverage_torch(low_buf, rows, frames, low_channels, out, offsets):
+    # THE DEFINITION: the summed-area table of dataset_video.collect_samples' coverage indicator, (c0 + c1) + c2 > 0 in fp32
+    for (_, off_low, _, H, W), start in zip(rows, offsets):
+        clip = low_buf[off_low:off_low + frames * low_channels * H * W].view(frames, low_channels, H, W)
+        for k, t in enumerate((0, frames - 1)):
+            covered = ((clip[t, 0] + clip[t, 1]) + clip[t, 2]) > 0
+            sat = torch.zeros((H + 1, W + 1), dtype=torch.int32, device=low_buf.device)
+            sat[1:, 1:] = covered.to(torch.int64).cumsum(0).cumsum(1).to(torch.int32)
+            at = start + k * (H + 1) * (W + 1)
+            out[at:at + sat.numel()].copy_(sat.reshape(-1))
+
+
+def clip_coverage(low_buf, table, frames, low_channels=5, rows=None):
+    """Summed-area tables of the crop-coverage indicator ``low[0] + low[1] + low[2] > 0`` of the first and the last frame of every clip
+    in the flat buffer ``low_buf``: a flat int32 tensor holding ``[2, H + 1, W + 1]`` per clip, one after the other
+    (``coverage_table_offsets``; a tensor ``[clips, 2, H + 1, W + 1]`` where the clips have one size).  ``table``: the int64 [clips, 5]
+    clip table on ``low_buf``'s device; ``rows``: its host copy where the caller has one (otherwise it is read back).  Device operands:
+    ONE launch of ``clip_coverage_kernel``, a workgroup per table.  CPU operands: the definition (``cumsum``)."""
+    if low_buf.dtype != torch.float32 or low_buf.dim() != 1 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 5:
+        raise ValueError("clip_coverage: a flat fp32 buffer and an int64 clip table [clips, 5]")
+    if table.device != low_buf.device or frames < 1 or low_channels < 3:
+        raise ValueError("clip_coverage: table on %s, buffer on %s, %d frames, %d channels" % (table.device, low_buf.device, frames, low_channels))
+    rows = [tuple(int(v) for v in row) for row in (table.tolist() if rows is None else rows)]
+    for k, (_, off_low, _, H, W) in enumerate(rows):
+        if H < 1 or W < 1 or not 0 <= off_low <= low_buf.numel() - frames * low_channels * H * W:
+            raise ValueError("clip_coverage: clip %d (%d x %d at %d) leaves the buffer of %d elements" % (k, H, W, off_low, low_buf.numel()))
+    offsets, total = coverage_table_offsets(rows)
+    out = torch.empty(total, dtype=torch.int32, device=low_buf.device)
+    lib = _sr() if low_buf.is_cuda else None
+    if lib is not None and hasattr(lib, "isrClipCoverage") and lib.isrClipCoverageSupported(len(rows), frames, low_channels) \
+            and low_buf.is_contiguous() and table.is_contiguous():
+        where = torch.tensor(offsets, dtype=torch.int64).to(low_buf.device)
+        with torch.cuda.device(low_buf.device):
+            rc = lib.isrClipCoverage(_ptr(low_buf), _ptr(table), _ptr(where), len(rows), frames, low_channels, _ptr(out), _stream())
+        if rc != 0:
+            raise RuntimeError("isrClipCoverage failed (%d)" % rc)
+    else:
+        if low_buf.is_cuda:
+            _warn_once("clip_coverage", "clip_coverage: the loaded library has no isrClipCoverage for %d clips; the PyTorch definition runs instead" % len(rows))
+        _clip_coverage_torch(low_buf, rows, frames, low_channels, out, offsets)
+    if len({(row[3], row[4]) for row in rows}) == 1:
+        out = out.view(len(rows), 2, rows[0][3] + 1, rows[0][4] + 1)
+    return out
 
 
 # ---- the viewer's display stage (viewer.py) --------------------------------------------------------------------------------------------
